@@ -13,6 +13,13 @@ microbatch of 16 sequences through all 36 layers + final norm + lm_head + greedy
           flight; hidden states move stage -> stage with RCCL send/recv over xGMI, greedy ids
           return last -> first.  Per-GPU work is fixed as N grows ("scaling": "weak").
 
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what the headline figure
+needs: set up, prefill, W warm-up steps, K timed steps, the outputs of the last timed step
+to `--dump-outputs DIR` if asked (next_ids.npy: the greedy ids the step returned; the inputs
+are seeded, the same in every run), one JSON line.  Everything else below (the per-kernel
+roofline, the re-measured peaks, the config-5 prefill lines, the stage projection, the CPU
+baselines, the N > 1 sub-layer split runs) is run and added to the line with `--full`.
+
 Before timing: every sequence is prefilled with 2048 tokens through the real prefill
 path (untimed; its rate is reported as `prefill`), so the KV cache holds real K/V.
 Timed region: K decode steps bracketed by barrier + synchronize; each stage's step of a
@@ -96,6 +103,19 @@ def measured_peaks(dev) -> dict:
                    "operands; HIP events, median of 5 after 3 warm-ups"}
 
 
+DUMP_MAX_BYTES = 64 << 20     # --dump-outputs: all files together
+
+
+def dump_outputs(dirname: str, arrays: dict) -> None:
+    """`--dump-outputs DIR`: every tensor of `arrays` as DIR/<name>.npy in float32 (exact for token
+    ids: vocab < 2^24), DUMP_MAX_BYTES in all (the greedy ids are a few hundred bytes)."""
+    import numpy as np
+    assert sum(t.numel() for t in arrays.values()) * 4 <= DUMP_MAX_BYTES, "--dump-outputs: over the size limit"
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(dirname, f"{name}.npy"), t.detach().to(torch.float32).cpu().numpy())
+
+
 def parse():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
@@ -105,6 +125,15 @@ def parse():
     p.add_argument("--batch", type=int, default=16)
     p.add_argument("--ctx", type=int, default=2048)
     p.add_argument("--seed", type=int, default=1234)
+    p.add_argument("--full", action="store_true",
+                   help="after the headline measurement also run everything else the benchmark measures: the "
+                        "per-kernel HIP-event pass and its roofline, the re-measured peaks, the config-5 prefill "
+                        "lines, the per-stage projection of the 2/4/8-GPU splits, the CPU baselines and (N > 1) the "
+                        "sub-layer split runs; the --no-* options below switch single parts of it off")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last timed step returned to its caller as "
+                        "DIR/next_ids.npy (float32 [microbatches, batch]): every sequence's greedy id (decode "
+                        "mode only)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-layers", type=int, default=2, help="layers timed by the CPU baseline sample")
     p.add_argument("--no-profile", action="store_true", help="skip the per-kernel HIP-event timing pass")
@@ -824,6 +853,9 @@ def pipeline_run(d, ranges, rank: int, world: int, dev, dist, args, profile: boo
         dist.barrier()
     elapsed = time.perf_counter() - t0
     tick = st.tick_stats
+    # what the last timed step handed back: every microbatch's greedy ids, which stage 0 holds when
+    # decode() returns (copied before the profile pass below decodes further)
+    next_ids = torch.stack(st.ids).cpu() if rank == 0 else None
     # ---- per-kernel HIP-event timings: the same decode kernels launched eagerly (events
     # cannot be timed inside a replayed graph); right after the timed region, same cache state
     prof = st.profile_decode(args.profile_steps) if profile else None
@@ -839,11 +871,13 @@ def pipeline_run(d, ranges, rank: int, world: int, dev, dist, args, profile: boo
         dist.all_reduce(stage_ms, op=dist.ReduceOp.SUM)
     stage_ms = [float(v) for v in stage_ms.cpu()]
     return {"st": st, "elapsed": elapsed, "t_prefill": t_prefill, "tick": tick, "prof": prof, "stage_ms": stage_ms,
-            "n_mb": n_mb, "shards": shards}
+            "n_mb": n_mb, "shards": shards, "next_ids": next_ids}
 
 
 def main():
     args = parse()
+    if args.dump_outputs and args.mode != "decode":
+        sys.exit("bench.py: --dump-outputs writes the decode run's ids; --mode prefill / stages have none")
     if args.mode == "prefill":
         return run_prefill(args)
     if args.mode == "stages":
@@ -900,8 +934,10 @@ def main():
     cal = None
     if vhead and not args.no_calibrate:
         cal = calibrate_shards(d, ranges, rank, world, dev, dist, args)
-    run = pipeline_run(d, ranges, rank, world, dev, dist, args, profile=not args.no_profile, vhead=vhead,
-                       shards=cal["shards"] if cal else None)
+    run = pipeline_run(d, ranges, rank, world, dev, dist, args, profile=args.full and not args.no_profile,
+                       vhead=vhead, shards=cal["shards"] if cal else None)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"next_ids": run["next_ids"]})
     st, elapsed, t_prefill, tick, prof, stage_ms = (run[k] for k in ("st", "elapsed", "t_prefill", "tick", "prof",
                                                                      "stage_ms"))
     n_mb = run["n_mb"]
@@ -982,9 +1018,12 @@ def main():
             "cpu_baseline": None,
             "ranks": ranks if world > 1 else None,
             "backend": None if not dist else dist.get_backend(),
+            "full": args.full,
         }
-        out["peaks_measured"] = measured_peaks(dev)
+        # everything below is beside the headline figure: `--full` only
+        out["peaks_measured"] = measured_peaks(dev) if args.full else None
         out["sublayer_split"] = None
+    if rank == 0 and args.full:
         if world == 1 and not args.no_prefill_line:
             # BASELINE config 5 in the same run (the driver's default bench call times it too)
             st.release()
@@ -1007,7 +1046,7 @@ def main():
             st.release()
             out["cpu_baseline"] = cpu_baseline(args.model, B, ctx, args.seed, args.cpu_layers)
             out["cpu_baseline_config1"] = cpu_config1(args.seed)
-    if world > 1 and not args.no_sublayer_split and args.split == "even" and not args.spans:
+    if world > 1 and args.full and not args.no_sublayer_split and args.split == "even" and not args.spans:
         # beside config 3's even split, same run: the sub-layer split chosen for the vocab-parallel
         # head (the projection's best-balanced split at 2, 4 and 8 stages) and north_star's
         # sub-layer split with the whole head on the last stage

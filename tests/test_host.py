@@ -248,6 +248,18 @@ def test_bench_stage_split_qwen3_8b():
     assert [k for _, k in bench.stage_split(d, 1, 16, 2048)] == [36]
 
 
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 .npy files, the ids exact; more than the size limit is refused."""
+    import bench
+    ids = torch.tensor([[151935, 0, 7], [1, 2, 3]], dtype=torch.int32)
+    bench.dump_outputs(str(tmp_path / "a"), {"next_ids": ids})
+    a = np.load(tmp_path / "a" / "next_ids.npy")
+    assert a.dtype == np.float32 and a.shape == (2, 3) and (a == ids.numpy()).all()
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 16)
+    with pytest.raises(AssertionError):
+        bench.dump_outputs(str(tmp_path / "b"), {"next_ids": ids})
+
+
 def test_build_decode_batch_descriptor():
     """inferd_kv_build_decode_batch (the descriptor a decode graph is captured on, advance = 1):
     reserves n_steps more tokens per sequence all or nothing, positions / slots start at 0 (the

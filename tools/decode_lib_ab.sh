@@ -6,7 +6,7 @@
 # usage: tools/decode_lib_ab.sh <name> [<name> ...]   -> gpurun_out/decode_ab/<i>_<name>.log
 set -o pipefail
 mkdir -p gpurun_out/decode_ab
-args="--steps 32 --warmup 4 --no-cpu-baseline --no-prefill-line"
+args="--full --steps 32 --warmup 4 --no-cpu-baseline --no-prefill-line"    # --full: the per-kernel pass
 i=0
 for n in base "$@" base; do
   i=$((i+1))
