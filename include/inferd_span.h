@@ -186,7 +186,8 @@ int inferd_span_set_weight(InferdSpan* span, int32_t layer, const char* name,
  *   x_out     optional device bf16 [n_tokens][hidden]: hidden after the last layer
  *   next_ids  last span only, optional: device int32 [n_seqs] greedy token of each
  *             sequence's last row (norm -> lm_head -> argmax, partitioned_models.py:162);
- *             ties resolve to the lowest index like torch.argmax
+ *             ties resolve to the lowest index like torch.argmax (after
+ *             inferd_span_set_sampling: a draw instead, see "Sampled decoding" below)
  *   logits    last span only, optional: device bf16 [n_seqs][vocab] last-row logits
  *   layer_out optional device bf16 [n_layers][n_tokens][hidden] per-layer capture */
 int inferd_span_forward(InferdSpan* span, const InferdBatch* batch, const int32_t* ids,
@@ -246,8 +247,55 @@ int inferd_span_step(InferdSpan* span, const InferdBatch* batch, int32_t advance
 /* Sticky device error flags, read and cleared (synchronises the device).  Bit 0: a token id
  * outside [0, vocab) reached the embedding gather (it reads row 0 instead; the reference's
  * nn.Embedding raises IndexError, so the Python host validates ids before the launch);
- * bit 1: a decode graph ran past the pages reserved for it. */
+ * bit 1: a decode graph ran past the pages reserved for it; bit 2 (added within ABI 5): a sampled
+ * row had more than INFERD_SAMPLE_MAX_KEPT columns at or above its top-k threshold (see below). */
 int inferd_span_error_flags(InferdSpan* span, int32_t* flags);
+
+/* ---- Sampled decoding (added within ABI 5: additions only, no existing struct or signature
+ * changes).  Replaces the reference client's sampling (client.py:95-120: transformers'
+ * temperature / top-k / top-p warpers, a softmax and torch.multinomial on the host; defaults
+ * 0.6 / 20 / 0.95, qwen3_config.py:5-7) with one kernel behind the lm_head GEMV, so a
+ * device-resident decode loop (inferd_span_step, a graph whose next_ids feed ids) can sample.
+ * One row's draw, l[c] = fp32 of the bf16 logit of column c (the values `logits` carries):
+ *   1. s[c] = l[c] / temperature (one fp32 division);
+ *   2. top-k: v_k = the min(top_k, vocab)-th largest s; every column with s >= v_k is kept -- ties
+ *      at v_k too, as TopKLogitsWarper keeps them -- ordered by (s descending, column ascending);
+ *      if more than INFERD_SAMPLE_MAX_KEPT columns qualify the first INFERD_SAMPLE_MAX_KEPT of
+ *      that order are kept and error flag bit 2 is set;
+ *   3. top-p (min_tokens_to_keep 1): q = fp32 softmax of the kept s; column j is removed iff the
+ *      sum of q over j and every column after it in the order is <= 1 - top_p; never the first;
+ *   4. q renormalised over what is left;
+ *   5. u in [0, 1) selects the first column of the order whose running sum exceeds u (none, by
+ *      rounding: the last one).  u = (splitmix64(key + pos) >> 40) * 2^-24, key =
+ *      splitmix64(splitmix64(seed) + row_seed), splitmix64 as in inferd_weightgen; pos = the
+ *      position the drawn token will occupy; row_seed = row_seeds[b], or b without row_seeds.
+ * A draw depends on (seed, row_seed, pos, the row's logits) only: not on the batch a row runs in,
+ * eager or graph launch, or the stage that owns the head.  Callers that split one batch over
+ * several calls (pipeline microbatches) pass distinct row_seeds.
+ * Ranges: temperature > 0, 1 <= top_k <= INFERD_SAMPLE_MAX_K, 0 < top_p <= 1; anything else is
+ * INFERD_ERR_ARG before any device call. */
+#define INFERD_SAMPLE_MAX_K 64
+#define INFERD_SAMPLE_MAX_KEPT 256
+typedef struct InferdSampling {
+  float temperature;
+  int32_t top_k;
+  float top_p;
+  uint64_t seed;
+  const uint64_t* row_seeds; /* device [n_seqs of the call], NULL: the row index */
+} InferdSampling;
+/* has_lm_head spans only (the vocab-parallel head would need a cross-shard top-k merge); NULL
+ * restores greedy.  Afterwards next_ids of inferd_span_forward / _step / _graph_capture is a draw
+ * with pos = ctx_lens[b] of the call's batch, read on the device (the parameters, row_seeds
+ * pointer included, are baked into a graph at capture).  A call that passes no `logits` stores
+ * them in a [64][vocab] bf16 buffer of the span, allocated by the first call here.  A span on
+ * which this was never called (or that was reset with NULL) launches exactly what it did before. */
+int inferd_span_set_sampling(InferdSpan* span, const InferdSampling* p);
+/* single op: logits bf16 [rows][vocab] row-major (16-byte aligned, vocab % 16 == 0, vocab <=
+ * 393216, rows <= 64), positions device int32 [rows]; outputs device: ids int32 [rows], optional
+ * u_out float [rows] (the uniform used), optional flags int32 [1] (bit 2 OR-ed in on capacity
+ * overflow). */
+int inferd_sample(const void* logits, int32_t rows, int32_t vocab, const InferdSampling* p,
+                  const int32_t* positions, int32_t* ids, float* u_out, int32_t* flags, void* stream);
 
 /* Per-kernel-class timing: HIP events recorded on the launch stream around every kernel of
  * the forward (classes below), up to max_pairs pairs; stop() synchronises on the events

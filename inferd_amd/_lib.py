@@ -40,6 +40,13 @@ class Batch(C.Structure):
                [(n, c_p) for n in ("seq_start", "positions", "slots", "ctx_lens", "block_table")]
 
 
+class Sampling(C.Structure):
+    """InferdSampling (added within ABI 5): row_seeds is a device uint64 pointer or None."""
+    _fields_ = [("temperature", c_f), ("top_k", c_i32), ("top_p", c_f), ("seed", c_u64), ("row_seeds", c_p)]
+
+
+SAMPLE_MAX_K, SAMPLE_MAX_KEPT = 64, 256   # INFERD_SAMPLE_MAX_K / INFERD_SAMPLE_MAX_KEPT
+
 SIGNATURES = {
     "inferd_last_error": (C.c_char_p, []),
     "inferd_abi_version": (C.c_int, []),
@@ -61,6 +68,8 @@ SIGNATURES = {
     "inferd_span_step": (C.c_int, [c_p, C.POINTER(Batch), c_i32, c_p, c_p, c_p, c_p, c_p, c_p]),
     "inferd_graph_destroy": (None, [c_p]),
     "inferd_span_error_flags": (C.c_int, [c_p, C.POINTER(c_i32)]),
+    "inferd_span_set_sampling": (C.c_int, [c_p, C.POINTER(Sampling)]),
+    "inferd_sample": (C.c_int, [c_p, c_i32, c_i32, C.POINTER(Sampling), c_p, c_p, c_p, c_p, c_p]),
     "inferd_span_kv_layer": (C.c_int, [c_p, c_i32, C.POINTER(c_p)]),
     "inferd_span_kv_clear": (C.c_int, [c_p, c_p]),
     "inferd_weightgen": (C.c_int, [c_p, c_i64, c_u64, c_u32, c_f, c_f, c_p]),

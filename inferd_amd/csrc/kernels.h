@@ -140,6 +140,18 @@ void launch_argmax_keys(const unsigned long long* partial, int n_tiles, int M, i
                         const unsigned long long* keys_in, unsigned long long* keys_out, int32_t* ids, hipStream_t s);
 void launch_argmax_combine(const unsigned long long* keys, int n_parts, int rows, int32_t* ids, hipStream_t s);
 
+// sampling.hip.  One draw per row of bf16 logits [rows][vocab] row-major (16-byte aligned, vocab % 16
+// == 0, at most SAMPLE_MAX_VOCAB): temperature, top-k (ties at the k-th value kept), top-p, then
+// the row's counter-based uniform selects a column (include/inferd_span.h "Sampled decoding").
+// keys: the lm_head GEMV's EPI_ARGMAX tile keys [rows][vocab / 16] of the same logits, or null (the
+// kernel then takes the tile maxima from the logits).  positions / row_seeds (null: the row index) /
+// ids / u_out (optional) / flags (optional; bit 2 OR-ed in when more than 256 columns qualify) are
+// device arrays over the rows.
+#define SAMPLE_MAX_VOCAB (16 * 24576)
+void launch_sample(const u16* logits, int rows, int vocab, const unsigned long long* keys, float temperature,
+                   int top_k, float top_p, uint64_t seed, const uint64_t* row_seeds, const int32_t* positions,
+                   int32_t* ids, float* u_out, int32_t* flags, hipStream_t s);
+
 // attention.hip
 struct AttnBatch {
   const int32_t* seq_start;    // [B+1] first token row of each sequence

@@ -109,6 +109,12 @@ struct InferdSpan {
   GemmWs gws;                 // prefill tail-split workspace (per span: spans never share tickets)
   float* qkv_part = nullptr;  // decode split-K q/k/v partials [QKV_KSL][16][qkv_rows]
   unsigned long long* argmax_partial = nullptr;
+  // sampled decoding (inferd_span_set_sampling): with sampling_on the head's next_ids are a draw
+  // (sampling.hip) instead of argmax_reduce; sample_logits [64][vocab] holds the logits of calls
+  // that pass none (allocated by the first set_sampling)
+  bool sampling_on = false;
+  InferdSampling sampling{};
+  u16* sample_logits = nullptr;
   int32_t* err = nullptr;
   // set by inferd_span_graph_capture(advance): the scheduler step the next forward's first
   // RMSNorm launch runs (NormPrologue) instead of a decode_advance_kernel node of its own
@@ -534,6 +540,8 @@ extern "C" int inferd_span_forward(InferdSpan* s, const InferdBatch* b, const in
     return fail(INFERD_ERR_ARG, "a span starting inside a gate/up projection needs x_in (the hand-off record)");
   if ((c.o_split_last || c.qkv_split_last) && !x_out)
     return fail(INFERD_ERR_ARG, "a span ending before an o projection or an attention needs x_out (the hand-off record)");
+  if (s->sampling_on && next_ids && logits && (uintptr_t)logits % 16)
+    return fail(INFERD_ERR_ARG, "a sampled head reads `logits` back: it must be 16-byte aligned");
   if (c.has_embed) {
     if (!ids) return fail(INFERD_ERR_ARG, "first span needs token ids");
     if (c.n_layers > 0) {
@@ -803,9 +811,17 @@ extern "C" int inferd_span_forward(InferdSpan* s, const InferdBatch* b, const in
     // path (DN_EXACT, as q/k/v) measured 213.8 us in the graph against 195 + 5 us (round 3).
     const bool pk_last = h % 32 == 0;
     launch_rmsnorm(x, h, b->seq_start + 1, 1, s->final_norm, s->last, h, B, h, c.rms_eps, st, pk_last);
-    GEMM_TRY(launch_gemm(s->last, h, s->lm_head, B, c.vocab, h, (u16*)logits, c.vocab, nullptr, 0, EPI_ARGMAX,
+    // a sampled head reads the logits of the tiles its keys select: they go to the span's own
+    // buffer when the caller wants none
+    const bool draw = s->sampling_on && next_ids;
+    u16* lg = (draw && !logits) ? s->sample_logits : (u16*)logits;
+    GEMM_TRY(launch_gemm(s->last, h, s->lm_head, B, c.vocab, h, lg, c.vocab, nullptr, 0, EPI_ARGMAX,
                 s->argmax_partial, st, nullptr, nullptr, nullptr, pk_last ? GEMM_PACK_A : 0));
-    if (next_ids) launch_argmax_reduce(s->argmax_partial, c.vocab / 16, B, next_ids, st);
+    if (draw)
+      launch_sample(lg, B, c.vocab, s->argmax_partial, s->sampling.temperature, s->sampling.top_k, s->sampling.top_p,
+                    s->sampling.seed, s->sampling.row_seeds, b->ctx_lens, next_ids, nullptr, s->err, st);
+    else if (next_ids)
+      launch_argmax_reduce(s->argmax_partial, c.vocab / 16, B, next_ids, st);
     s->prof_end(pe, st);
   }
   if (normed_out) {
@@ -844,6 +860,63 @@ extern "C" int inferd_span_head_shard(InferdSpan* s, const void* normed, int32_t
 extern "C" int inferd_argmax_combine(const uint64_t* keys, int32_t n_parts, int32_t rows, int32_t* ids, void* stream) {
   if (!keys || !ids || n_parts <= 0 || rows <= 0) return fail(INFERD_ERR_ARG, "bad argmax_combine args");
   launch_argmax_combine((const unsigned long long*)keys, n_parts, rows, ids, (hipStream_t)stream);
+  LAUNCH_CHECK();
+  return INFERD_OK;
+}
+
+// ------------------------------------------------------------------ sampled decoding
+// parameter ranges of InferdSampling, checked before any device call
+static int check_sampling(const InferdSampling* p) {
+  if (!(p->temperature > 0.f) || !(p->temperature <= 3.0e38f))
+    return fail(INFERD_ERR_ARG, "sampling: temperature must be > 0 (and finite)");
+  if (p->top_k < 1 || p->top_k > INFERD_SAMPLE_MAX_K)
+    return fail(INFERD_ERR_ARG, "sampling: top_k must be 1 .. " + std::to_string(INFERD_SAMPLE_MAX_K));
+  if (!(p->top_p > 0.f) || !(p->top_p <= 1.f)) return fail(INFERD_ERR_ARG, "sampling: top_p must be in (0, 1]");
+  return INFERD_OK;
+}
+
+extern "C" int inferd_span_set_sampling(InferdSpan* s, const InferdSampling* p) {
+  if (p) {
+    const int rc = check_sampling(p);
+    if (rc) return rc;
+  }
+  if (!s) return fail(INFERD_ERR_ARG, "null span");
+  if (!p) {
+    s->sampling_on = false;
+    return INFERD_OK;
+  }
+  if (!s->cfg.has_lm_head)
+    return fail(INFERD_ERR_ARG, "sampling needs a span with the whole lm_head (has_lm_head; the vocab-parallel head "
+                                "is greedy only)");
+  if (s->cfg.vocab > SAMPLE_MAX_VOCAB)
+    return fail(INFERD_ERR_ARG, "sampling: vocab must be <= " + std::to_string(SAMPLE_MAX_VOCAB));
+  if (!s->sample_logits) {
+    // on the span's own device (where its buffers live), whichever device the caller has current
+    hipPointerAttribute_t at;
+    int cur = 0;
+    HIP_TRY(hipPointerGetAttributes(&at, s->err));
+    HIP_TRY(hipGetDevice(&cur));
+    if (at.device != cur) HIP_TRY(hipSetDevice(at.device));
+    const int rc = s->alloc((void**)&s->sample_logits, (size_t)64 * s->cfg.vocab * 2);
+    if (at.device != cur) (void)hipSetDevice(cur);
+    if (rc) return rc;
+  }
+  s->sampling = *p;
+  s->sampling_on = true;
+  return INFERD_OK;
+}
+
+extern "C" int inferd_sample(const void* logits, int32_t rows, int32_t vocab, const InferdSampling* p,
+                             const int32_t* positions, int32_t* ids, float* u_out, int32_t* flags, void* stream) {
+  if (!p) return fail(INFERD_ERR_ARG, "sample: null parameters");
+  const int rc = check_sampling(p);
+  if (rc) return rc;
+  if (!logits || !positions || !ids) return fail(INFERD_ERR_ARG, "sample: logits, positions and ids are required");
+  if (rows < 1 || rows > 64 || vocab < 16 || vocab % 16 || vocab > SAMPLE_MAX_VOCAB)
+    return fail(INFERD_ERR_ARG, "sample: rows 1 .. 64, vocab a multiple of 16 up to " + std::to_string(SAMPLE_MAX_VOCAB));
+  if ((uintptr_t)logits % 16) return fail(INFERD_ERR_ARG, "sample: logits must be 16-byte aligned");
+  launch_sample((const u16*)logits, rows, vocab, nullptr, p->temperature, p->top_k, p->top_p, p->seed, p->row_seeds,
+                positions, ids, u_out, flags, (hipStream_t)stream);
   LAUNCH_CHECK();
   return INFERD_OK;
 }

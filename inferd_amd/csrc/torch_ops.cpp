@@ -15,7 +15,9 @@
 #include <torch/custom_class.h>
 #include <torch/library.h>
 
+#include <mutex>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "../../include/inferd_span.h"
@@ -108,7 +110,68 @@ int64_t span_create(at::IntArrayRef cfg, double rms_eps, double rope_theta, at::
   return reinterpret_cast<int64_t>(s);
 }
 
-void span_destroy(int64_t span) { inferd_span_destroy(handle<InferdSpan>(span, "span_destroy")); }
+// the row_seeds tensor of each span's sampling setting (the span keeps its device pointer)
+std::mutex g_seeds_mu;
+std::unordered_map<int64_t, at::Tensor> g_row_seeds;
+
+void span_destroy(int64_t span) {
+  inferd_span_destroy(handle<InferdSpan>(span, "span_destroy"));
+  std::lock_guard<std::mutex> l(g_seeds_mu);
+  g_row_seeds.erase(span);
+}
+
+// Sampled decoding (inferd_span_set_sampling): on = false restores greedy.  row_seeds: int64 (the
+// uint64 bits) on the span's device, one per sequence of the calls that follow; held alive here
+// until the setting changes or the span is destroyed (and by every DecodeGraph captured under it).
+// The first call allocates the span's logits buffer: the library places it on the span's own device
+// whichever device is current here.
+void span_set_sampling(int64_t span, double temperature, int64_t top_k, double top_p, int64_t seed,
+                       const std::optional<at::Tensor>& row_seeds, bool on) {
+  InferdSpan* s = handle<InferdSpan>(span, "span_set_sampling");
+  if (!on) {
+    ok(inferd_span_set_sampling(s, nullptr), "span_set_sampling");
+    std::lock_guard<std::mutex> l(g_seeds_mu);
+    g_row_seeds.erase(span);
+    return;
+  }
+  TORCH_CHECK(top_k >= INT32_MIN && top_k <= INT32_MAX, "span_set_sampling: top_k out of range");
+  if (row_seeds) {
+    TORCH_CHECK(row_seeds->is_cuda(), "span_set_sampling: row_seeds must be on the span's GPU");
+    check_arg(row_seeds, row_seeds->device(), at::kLong, 1, "row_seeds");
+  }
+  const InferdSampling p{(float)temperature, (int32_t)top_k, (float)top_p, (uint64_t)seed,
+                         (const uint64_t*)opt_ptr(row_seeds)};
+  std::optional<c10::hip::HIPGuard> g;
+  if (row_seeds) g.emplace(row_seeds->device().index());
+  ok(inferd_span_set_sampling(s, &p), "span_set_sampling");
+  std::lock_guard<std::mutex> l(g_seeds_mu);
+  if (row_seeds)
+    g_row_seeds[span] = *row_seeds;
+  else
+    g_row_seeds.erase(span);
+}
+
+// the single op (inferd_sample): one draw per row of logits bf16 [rows, vocab]
+void sample(const at::Tensor& logits, double temperature, int64_t top_k, double top_p, int64_t seed,
+            const std::optional<at::Tensor>& row_seeds, const at::Tensor& positions, const at::Tensor& ids,
+            const std::optional<at::Tensor>& u_out, const std::optional<at::Tensor>& flags) {
+  TORCH_CHECK(logits.is_cuda() && logits.dim() == 2, "sample: logits must be a [rows, vocab] GPU tensor");
+  TORCH_CHECK(top_k >= INT32_MIN && top_k <= INT32_MAX, "sample: top_k out of range");
+  const at::Device dev = logits.device();
+  const int64_t rows = logits.size(0), vocab = logits.size(1);
+  check_arg(logits, dev, at::kBFloat16, 0, "logits");
+  check_arg(row_seeds, dev, at::kLong, rows, "row_seeds");
+  check_arg(positions, dev, at::kInt, rows, "positions");
+  check_arg(ids, dev, at::kInt, rows, "ids");
+  check_arg(u_out, dev, at::kFloat, rows, "u_out");
+  check_arg(flags, dev, at::kInt, 1, "flags");
+  const InferdSampling p{(float)temperature, (int32_t)top_k, (float)top_p, (uint64_t)seed,
+                         (const uint64_t*)opt_ptr(row_seeds)};
+  c10::hip::HIPGuard g(dev.index());
+  ok(inferd_sample(logits.data_ptr(), (int32_t)rows, (int32_t)vocab, &p, positions.data_ptr<int32_t>(),
+                   ids.data_ptr<int32_t>(), (float*)opt_ptr(u_out), (int32_t*)opt_ptr(flags), stream_of(dev)),
+     "sample");
+}
 
 std::vector<int64_t> span_config(int64_t span) {
   const InferdSpanConfig c = config_of(handle<InferdSpan>(span, "span_config"));
@@ -363,6 +426,11 @@ struct DecodeGraph : torch::CustomClassHolder {
     check_forward_args(config_of(s), words, b, ids, x, x_out, next_ids, logits, std::nullopt);
     for (const auto* o : {&ids, &x, &x_out, &next_ids, &logits})
       if (*o) keep.push_back(**o);
+    {  // a sampled span's row_seeds pointer is baked into the graph too
+      std::lock_guard<std::mutex> l(g_seeds_mu);
+      auto it = g_row_seeds.find(span);
+      if (it != g_row_seeds.end()) keep.push_back(it->second);
+    }
     // capture on a side stream (the legacy default stream cannot capture), ordered after the
     // current stream's work and before its later work
     c10::hip::HIPStream cs = c10::hip::getStreamFromPool(false, device.index());
@@ -426,6 +494,12 @@ TORCH_LIBRARY(inferd, m) {
         "Tensor(b!)? next_ids, Tensor(c!)? logits, Tensor(d!)? layers=None) -> ()",
         &span_forward);
   m.def("span_lm_head(int span, Tensor x, Tensor(a!) logits) -> ()", &span_lm_head);
+  m.def("span_set_sampling(int span, float temperature, int top_k, float top_p, int seed, Tensor? row_seeds, "
+        "bool on) -> ()",
+        &span_set_sampling);
+  m.def("sample(Tensor logits, float temperature, int top_k, float top_p, int seed, Tensor? row_seeds, "
+        "Tensor positions, Tensor(a!) ids, Tensor(b!)? u_out, Tensor(c!)? flags) -> ()",
+        &sample);
   m.def("span_head_shard(int span, Tensor normed, int rows, Tensor? keys_in, Tensor(a!)? keys_out, "
         "Tensor(b!)? ids, Tensor(c!)? logits=None) -> ()",
         &span_head_shard);

@@ -163,6 +163,14 @@ class SpanGroup(PartitionedQwen2):
         elif model_in.numel() != rows * self.dims.hidden:
             raise ValueError(f"hidden rows of {tuple(model_in.shape)} for {rows} request tokens")
 
+    def _sampling(self, inputs):
+        """A group of more than one rank answers greedily only: rank 0 takes the request, the
+        group's last rank owns the head, and the setting is not carried between them."""
+        if self.world > 1 and isinstance(inputs, dict) and inputs.get("sampling") is not None:
+            raise ValueError('"sampling" is not supported by a multi-GPU span group (world > 1): it decodes '
+                             "greedily only; serve the last stage from a single-GPU PartitionedQwen2 to sample")
+        return super()._sampling(inputs)
+
     @torch.no_grad()
     def _run(self, requests, model_in):
         rows = sum(n for _, n in requests)

@@ -28,11 +28,15 @@ Differences, all on purpose:
     once by `python -m inferd_amd.convert_parts` (an inert unpickler: nothing in the file
     runs) instead of being loaded;
   * an optional "session_id" in the input dict keeps K/V per sequence on every stage
-    (PartitionedQwen2 docstring); without it the protocol is the reference's, unchanged.
+    (PartitionedQwen2 docstring); without it the protocol is the reference's, unchanged;
+  * an optional "sampling" in the input dict makes the last stage draw the next token on the
+    device (temperature / top-k / top-p, the reference client's decoding mode, client.py:95-120)
+    instead of taking argmax (PartitionedQwen2 docstring).
 """
 from __future__ import annotations
 
 import base64
+import hashlib
 import json
 import os
 from collections import OrderedDict
@@ -40,7 +44,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from .runtime import MODELS, ModelDims, SpanRuntime
+from .runtime import MODELS, ModelDims, SpanRuntime, check_sampling_params
 from .semantics import check_bool_causal_mask
 
 _BF16 = "bfloat16"
@@ -76,6 +80,30 @@ def build_decoder_attention_mask(attn_mask_2d: torch.Tensor) -> torch.Tensor:
     causal = causal.unsqueeze(0).unsqueeze(1)
     padding = attn_mask_2d.unsqueeze(1).unsqueeze(2).to(torch.bool)
     return padding & causal
+
+
+def session_row_seed(session_id) -> int:
+    """The 64-bit row seed of a session's draws: the first 8 bytes of blake2b over the id's text --
+    the same on every node and in every process (never Python's salted hash); 0 without a session."""
+    if session_id is None:
+        return 0
+    return int.from_bytes(hashlib.blake2b(str(session_id).encode("utf-8"), digest_size=8).digest(), "little")
+
+
+_SAMPLING_KEYS = ("temperature", "top_k", "top_p", "seed")
+
+
+def _sampling_of(inputs):
+    """The validated "sampling" entry of an input dict, or None."""
+    if not isinstance(inputs, dict) or inputs.get("sampling") is None:
+        return None
+    sp = inputs["sampling"]
+    if not isinstance(sp, dict) or any(k not in sp for k in _SAMPLING_KEYS):
+        raise ValueError(f'"sampling" must be a dict with {", ".join(_SAMPLING_KEYS)}')
+    check_sampling_params(sp["temperature"], sp["top_k"], sp["top_p"])
+    if not isinstance(sp["seed"], int) or isinstance(sp["seed"], bool):
+        raise ValueError('"sampling": seed must be an int')
+    return {k: sp[k] for k in _SAMPLING_KEYS}
 
 
 # ------------------------------------------------------------------ stage modules
@@ -265,7 +293,14 @@ class PartitionedQwen2:
     instead of raising; later stages pass that answer through (dropping their own copy), so it
     reaches the client as the chain's result.  The client resends the same generated_ids with
     "restart_session": True, and stage 0 recomputes the session from position 0 (every
-    downstream stage then restarts it too: past_len 0)."""
+    downstream stage then restarts it too: past_len 0).
+
+    Sampled (optional): an input dict that carries "sampling": {"temperature", "top_k", "top_p",
+    "seed"} travels down the chain like "session_id"; the last stage sets it on its span for that
+    call (SpanRuntime.set_sampling) and clears it afterwards, so next_token_id is a draw at the
+    token's position with the row seed session_row_seed(session_id) (0 for a stateless call): the
+    same seed, session and prefix give the same token on any node.  Without the key the answer
+    is greedy.  A stage whose head is vocab-parallel raises ValueError (that head is greedy only)."""
 
     def __init__(self, model_name: str, num_stages: int, stage: int, parts_path: str):
         self.stage = stage
@@ -325,10 +360,33 @@ class PartitionedQwen2:
         """partitioned_models.py:145-168 (same output schema)."""
         if isinstance(inputs, dict) and "session_id" in inputs:
             return self._forward_session(inputs)
+        sampling = self._sampling(inputs)
         gen_ids, model_in = self._prepare_inputs(inputs)
         T = model_in.size(1)
-        out = self._run([(None, T)], model_in)
-        return self._output(out, gen_ids, T, {})
+        out = self._run_sampled([(None, T)], model_in, sampling, None)
+        return self._output(out, gen_ids, T, self._sampling_extra(sampling))
+
+    def _sampling(self, inputs):
+        sampling = _sampling_of(inputs)
+        if sampling is not None and (self.span.head_rows or self.span.final_norm_out):
+            raise ValueError('"sampling" needs the last stage to own the whole lm_head: the vocab-parallel head is '
+                             "greedy only")
+        return sampling
+
+    def _sampling_extra(self, sampling):
+        """non-last stages hand the setting on, as they do session_id"""
+        return {"sampling": sampling} if sampling is not None and not self._last else {}
+
+    def _run_sampled(self, requests, model_in, sampling, session_id):
+        """_run, the last stage drawing instead of taking argmax while `sampling` is set"""
+        if sampling is None or not self._last:
+            return self._run(requests, model_in)
+        self.span.set_sampling(sampling["temperature"], sampling["top_k"], sampling["top_p"], sampling["seed"],
+                               row_seeds=[session_row_seed(session_id)])
+        try:
+            return self._run(requests, model_in)
+        finally:
+            self.span.clear_sampling()
 
     # compute / cache hooks (inferd_amd.node_group runs them across a multi-GPU group)
     @torch.no_grad()
@@ -369,6 +427,7 @@ class PartitionedQwen2:
         if inputs.get("session_lost"):         # an upstream stage lost it: pass the answer on
             self.close_session(sid)
             return {"session_id": sid, "session_lost": True, "generated_ids": inputs.get("generated_ids")}
+        sampling = self._sampling(inputs)
         gen_ids, model_in = self._prepare_inputs(inputs)
         key = ("sess", sid)
         past = self._cached_len(key)
@@ -396,9 +455,9 @@ class PartitionedQwen2:
             except RuntimeError as e:
                 if "KV pool exhausted" not in str(e) or not self._evict_other(sid):
                     raise
-        out = self._run([(key, n)], new)
+        out = self._run_sampled([(key, n)], new, sampling, sid)
         self._touch(sid, (model_in.reshape(-1).tolist() if self.stage == 0 else past + n))
-        return self._output(out, gen_ids, n, {"session_id": sid, "past_len": past})
+        return self._output(out, gen_ids, n, {"session_id": sid, "past_len": past, **self._sampling_extra(sampling)})
 
     def _evict_other(self, sid):
         for old in list(self._sessions):

@@ -79,6 +79,54 @@ def gen_tensor(seed: int, tid: int, shape, norm: bool, device) -> torch.Tensor:
     return t.reshape(tuple(shape))
 
 
+SAMPLE_MAX_K, SAMPLE_MAX_KEPT = 64, 256   # INFERD_SAMPLE_MAX_K / INFERD_SAMPLE_MAX_KEPT
+
+
+def check_sampling_params(temperature, top_k, top_p):
+    """The ranges of a sampling setting (InferdSampling): ValueError before anything is launched."""
+    if not (isinstance(temperature, (int, float)) and 0.0 < float(temperature) < float("inf")):
+        raise ValueError(f"sampling: temperature must be > 0, got {temperature!r}")
+    if not (isinstance(top_k, int) and not isinstance(top_k, bool) and 1 <= top_k <= SAMPLE_MAX_K):
+        raise ValueError(f"sampling: top_k must be an int in 1 .. {SAMPLE_MAX_K}, got {top_k!r}")
+    if not (isinstance(top_p, (int, float)) and 0.0 < float(top_p) <= 1.0):
+        raise ValueError(f"sampling: top_p must be in (0, 1], got {top_p!r}")
+
+
+def _i64(v: int) -> int:
+    """the int64 carrying the bits of a 64-bit unsigned value (torch ops take int64)"""
+    v = int(v) & 0xFFFFFFFFFFFFFFFF
+    return v - (1 << 64) if v >= (1 << 63) else v
+
+
+def row_seed_tensor(row_seeds, device) -> torch.Tensor:
+    """Row seeds (64-bit unsigned ints, or an int64 tensor already holding their bits) as the int64
+    device tensor the engine reads."""
+    if isinstance(row_seeds, torch.Tensor):
+        return row_seeds.to(device=device, dtype=torch.int64).contiguous()
+    return torch.tensor([_i64(v) for v in row_seeds], dtype=torch.int64, device=device)
+
+
+def sample(logits: torch.Tensor, temperature: float, top_k: int, top_p: float, seed: int, positions, row_seeds=None,
+           want_u: bool = False, flags: torch.Tensor | None = None):
+    """One draw per row of `logits` (bf16 [rows <= 64, vocab] on a GPU) -- the single op behind the
+    sampled head (torch.ops.inferd.sample; include/inferd_span.h "Sampled decoding"): temperature,
+    top-k (ties kept), top-p, then the counter-based uniform of (seed, row seed, position).
+    positions: int [rows], the position each drawn token will occupy; row_seeds: optional 64-bit
+    ints [rows] (default: the row index); flags: optional int32 [1] device tensor, bit 2 OR-ed in
+    when a row has more than 256 columns at its top-k threshold.  Returns ids int32 [rows], and the
+    uniforms float32 [rows] with want_u.  Stream ordered, no sync."""
+    check_sampling_params(temperature, top_k, top_p)
+    dev = logits.device
+    with torch.cuda.device(dev):
+        lg = logits.to(torch.bfloat16).contiguous()
+        pos = torch.as_tensor(positions).to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+        rs = None if row_seeds is None else row_seed_tensor(row_seeds, dev)
+        ids = torch.empty(lg.shape[0], dtype=torch.int32, device=dev)
+        u = torch.empty(lg.shape[0], dtype=torch.float32, device=dev) if want_u else None
+        T.sample(lg, float(temperature), int(top_k), float(top_p), _i64(seed), rs, pos, ids, u, flags)
+    return (ids, u) if want_u else ids
+
+
 class Batch:
     """A batch descriptor: the device (or host) int32 words [seq_start | positions | slots |
     ctx_lens | block_table] the native table wrote and their shape [n_seqs, n_tokens, max_q_len,
@@ -173,13 +221,21 @@ class DecodeGraph:
     `ids` and `next_ids` may alias (greedy feedback on a single-span model).  Pages for
     `n_steps` tokens are reserved up front; launching more than n_steps times raises.
     `logits` (last span, optional): bf16 [sessions, vocab] receives every replay's last-row
-    logits."""
+    logits.
+    A span with a sampling setting (SpanRuntime.set_sampling) captures the sampled head: the
+    setting -- parameters, seed and the row_seeds tensor, one entry per session in order -- is baked
+    into the graph at capture; later set_sampling / clear_sampling calls do not change it.  Every
+    replay draws at the position its token will occupy, so launch() and launch_eager() from the
+    same state give the same ids."""
 
     def __init__(self, span: "SpanRuntime", sessions, n_steps: int, ids=None, x=None, hidden_out=None,
                  next_ids=None, logits=None):
         self.span, self.n_steps = span, n_steps
         # reserve(sid, 0) enters a never-prefilled session into the native table (empty), so a
         # graph may also start a session from position 0
+        sessions = list(sessions)
+        if next_ids is not None:
+            span._check_seed_count(len(sessions))
         self.states = [span.reserve(sid, 0) for sid in sessions]
         with torch.cuda.device(span.device):
             self.graph = torch.classes.inferd.DecodeGraph(span.handle, span.kv.handle, [st.seq for st in self.states],
@@ -249,6 +305,8 @@ class SpanRuntime:
         self.handle = T.span_create(cfg, dims.eps, dims.rope_theta, self.device)
         self.kv = KvTable(kv_pages)
         self.sessions: dict = {}   # session key -> SeqView
+        self.sampling = None       # (temperature, top_k, top_p, seed) while set_sampling holds
+        self._row_seeds = None     # its row-seed tensor (int64, device) or None: the row index
         self._seq_ids = itertools.count(1)
 
     def __del__(self):
@@ -339,8 +397,49 @@ class SpanRuntime:
         f = T.span_error_flags(self.handle, self.device)
         if f & 1:
             raise IndexError("index out of range in self (token id outside the vocabulary)")
-        if f:
+        if f & 2:
             raise RuntimeError(f"span device error flags 0x{f:x} (decode slot overflow)")
+        if f & 4:
+            raise RuntimeError(f"span device error flags 0x{f:x} (sampling: more than {SAMPLE_MAX_KEPT} columns at "
+                               "or above a row's top-k threshold; the first of them in (logit, column) order "
+                               "were kept)")
+        if f:
+            raise RuntimeError(f"span device error flags 0x{f:x}")
+
+    # ----------------------------------------------------------------- sampled decoding
+    def set_sampling(self, temperature: float, top_k: int, top_p: float, seed: int, row_seeds=None):
+        """From now on next_ids of forward / run / a DecodeGraph captured afterwards are draws, not
+        argmax (include/inferd_span.h "Sampled decoding": temperature, top-k with ties kept, top-p,
+        a counter-based uniform of (seed, row seed, position)).  row_seeds: 64-bit ints, one per
+        sequence of the calls that follow, in request order (default: the request's index); a call
+        with more sequences than seeds raises ValueError.  forward() keeps request i on row seed i
+        of this list when it cuts the requests into several engine calls; run() and a DecodeGraph
+        read them by the row of their batch.  Pass distinct seeds when one batch is split over
+        several forward / run calls (pipeline microbatches), or a session's draws would repeat
+        another's.  Spans with the whole lm_head only."""
+        check_sampling_params(temperature, top_k, top_p)
+        if not self.has_lm_head:
+            raise ValueError("sampling needs the span with the whole lm_head (the vocab-parallel head is greedy only)")
+        with torch.cuda.device(self.device):
+            rs = None if row_seeds is None else row_seed_tensor(row_seeds, self.device)
+            T.span_set_sampling(self.handle, float(temperature), int(top_k), float(top_p), _i64(seed), rs, True)
+        self.sampling = (float(temperature), int(top_k), float(top_p), int(seed))
+        self._row_seeds = rs
+
+    def _point_seeds(self, rs):
+        """the current setting with another row-seed tensor (forward: one engine call's requests)"""
+        t, k, p, seed = self.sampling
+        T.span_set_sampling(self.handle, t, k, p, _i64(seed), rs, True)
+
+    def _check_seed_count(self, n_seqs: int):
+        if self.sampling is not None and self._row_seeds is not None and self._row_seeds.numel() < n_seqs:
+            raise ValueError(f"sampling: {self._row_seeds.numel()} row_seeds for a call of {n_seqs} sequences")
+
+    def clear_sampling(self):
+        """Back to greedy next_ids (exactly the launches of a span that never sampled)."""
+        T.span_set_sampling(self.handle, 1.0, 1, 1.0, 0, None, False)
+        self.sampling = None
+        self._row_seeds = None
 
     # ----------------------------------------------------------------- sessions
     def release(self, session_id):
@@ -366,6 +465,8 @@ class SpanRuntime:
     def run(self, batch, ids=None, x=None, hidden=None, next_ids=None, logits=None, layers=None, stream=None):
         """Launch one span forward on a prebuilt Batch with caller-owned device tensors
         (no host sync, no allocation).  Used by the pipeline runtime and the bench."""
+        if next_ids is not None:
+            self._check_seed_count(batch.n_seqs)
         if stream is None:
             T.span_forward(self.handle, batch.words, batch.shape, ids, x, hidden, next_ids, logits, layers)
         else:
@@ -448,6 +549,8 @@ class SpanRuntime:
         if len(set(sids)) != len(sids):
             raise ValueError("a session may appear only once per forward call")
         total = sum(n for _, n in requests)
+        if want_next_ids and self.has_lm_head:
+            self._check_seed_count(len(requests))
         # hand-off records (InferdSpanConfig): decode calls at a gate/up boundary, every call at an
         # attention|o boundary (the attention output fragment-packed in a pure decode call)
         pure = all(n == 1 for _, n in requests)
@@ -492,7 +595,7 @@ class SpanRuntime:
                 else:
                     st = self._seq(sid)
                 states.append(st)
-            ok, advanced = False, False
+            ok, advanced, seeds_all = False, False, None
             try:
                 for st, (_, n) in zip(states, requests):
                     self.kv.reserve(st.seq, n)
@@ -530,7 +633,16 @@ class SpanRuntime:
                     raise ValueError("across an attention|o boundary a forward call is one engine call "
                                      f"(at most {self.max_tokens} tokens / {self.max_seqs} sequences)")
                 keep = []
+                # a sampled head reads its row seed by the row of the engine call: with several
+                # engine calls every call gets the seeds of its own requests (a call's rows are
+                # consecutive requests), so request i draws with row seed i however it was cut
+                if self.sampling is not None and nid is not None and len(calls) > 1:
+                    seeds_all = self._row_seeds[:B] if self._row_seeds is not None else \
+                        torch.arange(B, dtype=torch.int64, device=dev)
+                    keep.append(seeds_all)
                 for call in calls:
+                    if seeds_all is not None:
+                        self._point_seeds(seeds_all[call[0][0]:call[0][0] + len(call)])
                     r0 = row0[call[0][0]] + call[0][1]
                     m = sum(t for _, _, t in call)
                     single = len(calls) == 1
@@ -564,6 +676,8 @@ class SpanRuntime:
                         keep.append((c_nid, c_lg, c_lay))
                 ok = True
             finally:
+                if seeds_all is not None:
+                    self._point_seeds(self._row_seeds)
                 for st in temp:
                     self.kv.release(st.seq)
                 if not ok and advanced:   # a chunked call that failed part-way leaves no
