@@ -116,10 +116,6 @@ struct InferdSpan {
   InferdSampling sampling{};
   u16* sample_logits = nullptr;
   int32_t* err = nullptr;
-  // set by inferd_span_graph_capture(advance): the scheduler step the next forward's first
-  // RMSNorm launch runs (NormPrologue) instead of a decode_advance_kernel node of its own
-  NormPrologue adv;
-  bool adv_pending = false;
   std::vector<void*> allocs;
   // optional per-kernel-class timing with HIP events on the launch stream
   bool prof_on = false;
@@ -160,14 +156,15 @@ struct InferdSpan {
   // layer; has_o: o_proj + residual
   bool first_no_attn() const { return cfg.skip_first_attn || cfg.o_split_first; }
   bool last_qkv_only(int l) const { return l == cfg.n_layers - 1 && cfg.qkv_split_last; }
+  // layer l is the MLP half a span starts at / ends in a hand-off record (before its attention or o)
+  bool mlp_only(int l) const { return l == 0 && cfg.skip_first_attn; }
+  bool ends_in_record(int l) const { return l == cfg.n_layers - 1 && (cfg.o_split_last || cfg.qkv_split_last); }
+  // layer l's q/k/v rows arrive in x_in's record: pure decode calls at a q/k/v|attention boundary
+  bool qkv_in_record(int l, bool decode) const { return l == 0 && cfg.qkv_split_first && decode; }
   bool has_qkv(int l) const { return !(l == 0 && first_no_attn()); }
   bool has_attn(int l) const { return has_qkv(l) && !last_qkv_only(l); }
-  bool has_o(int l) const {
-    return !(l == 0 && cfg.skip_first_attn) && !(l == cfg.n_layers - 1 && cfg.o_split_last) && !last_qkv_only(l);
-  }
-  bool has_mlp(int l) const {
-    return !(l == cfg.n_layers - 1 && (cfg.skip_last_mlp || cfg.o_split_last)) && !last_qkv_only(l);
-  }
+  bool has_o(int l) const { return !mlp_only(l) && !ends_in_record(l); }
+  bool has_mlp(int l) const { return !(l == cfg.n_layers - 1 && cfg.skip_last_mlp) && !ends_in_record(l); }
   // the last layer of a span that ends inside the layer's gate/up projection computes part of it
   bool has_gateup(int l) const { return has_mlp(l) || (l == cfg.n_layers - 1 && cfg.gateup_split_last); }
   int kv_layers() const { return cfg.n_layers - (first_no_attn() ? 1 : 0) - (cfg.qkv_split_last ? 1 : 0); }
@@ -511,328 +508,333 @@ static AttnBatch to_attn(const InferdBatch* b) {
   return a;
 }
 
-extern "C" int inferd_span_forward(InferdSpan* s, const InferdBatch* b, const int32_t* ids,
-                                   const void* x_in, void* x_out, int32_t* next_ids, void* logits,
-                                   void* layer_out, void* stream) {
-  if (!s) return fail(INFERD_ERR_ARG, "null span");
-  int rc = check_batch(s, b);
-  if (rc) return rc;
+namespace {
+// One forward call, on its caller's stack: the arguments (the first seven members), what follows
+// from them for the whole call, and the residual cursor.  Every helper returns INFERD_OK or fail().
+struct Forward {
+  InferdSpan* const s;
+  const InferdBatch* const b;
+  const void* const x_in;
+  // a final_norm_out span: the caller's x_out receives the final-normed last rows (normed_out,
+  // head()); the last layer's hidden rows stay in the workspace, as on a span with lm_head
+  void* const x_out;
+  void* const normed_out;
+  void* const layer_out;
+  const hipStream_t st;
   const InferdSpanConfig& c = s->cfg;
-  hipStream_t st = (hipStream_t)stream;
   const int M = b->n_tokens, B = b->n_seqs;
-  const int h = c.hidden, I = c.intermediate, H = c.heads, KV = c.kv_heads;
-  const int qkvN = s->qkv_rows();
+  const int h = c.hidden, I = c.intermediate, H = c.heads, KV = c.kv_heads, qkvN = s->qkv_rows();
   const float scale = 1.0f / sqrtf((float)HEAD_DIM);
-  const u16* x;
-  // the first RMSNorm launch (layer 0's input norm) also runs the embedding gather and a
-  // pending graph scheduler step (kernels.h NormPrologue): two graph nodes fewer per step
-  NormPrologue pro;
-  if (s->adv_pending) {
-    pro = s->adv;
-    s->adv_pending = false;
-  }
-  // a final_norm_out span: x_out receives the final-normed last rows (below); the last layer's
-  // hidden rows stay in the workspace, as on a span with lm_head
-  void* const normed_out = c.final_norm_out ? x_out : nullptr;
-  if (c.final_norm_out) x_out = nullptr;
-  if (normed_out && B > 64) return fail(INFERD_ERR_ARG, "final_norm_out supports <= 64 sequences per call");
-  if (M <= 64 && c.gateup_split_first && !x_in)
-    return fail(INFERD_ERR_ARG, "a span starting inside a gate/up projection needs x_in (the hand-off record)");
-  if ((c.o_split_last || c.qkv_split_last) && !x_out)
-    return fail(INFERD_ERR_ARG, "a span ending before an o projection or an attention needs x_out (the hand-off record)");
-  if (s->sampling_on && next_ids && logits && (uintptr_t)logits % 16)
-    return fail(INFERD_ERR_ARG, "a sampled head reads `logits` back: it must be 16-byte aligned");
-  if (c.has_embed) {
-    if (!ids) return fail(INFERD_ERR_ARG, "first span needs token ids");
-    if (c.n_layers > 0) {
-      pro.ids = ids;
-      pro.table = s->embed;
-      pro.vocab = c.vocab;
-      pro.err = s->err;
-      pro.x_out = s->h;
-    } else {
-      launch_embed(ids, s->embed, M, h, c.vocab, s->h, s->err, st);
-    }
-    x = s->h;
-  } else {
-    if (!x_in) return fail(INFERD_ERR_ARG, "span needs x_in hidden states");
-    x = (const u16*)x_in;
-  }
-  if (c.n_layers == 0 && x_out && x != x_out)
-    HIP_TRY(hipMemcpyAsync(x_out, x, (size_t)M * h * 2, hipMemcpyDeviceToDevice, st));
   const AttnBatch ab = to_attn(b);
   // RMSNorms (qwen3_server_module.py:19-25, :173-176): see InferdSpan::ssq_in.  gemv: every
   // projection of this call is a decode GEMV (<= 64 rows), so the o / down GEMVs can hand the
   // next norm its row sums of squares.
   const bool gemv = M <= 64;
-  auto slot = [&](int i) { return s->ssq + (size_t)i * SSQ_SLOT_WORDS; };
   // decode: the residual stream between layers (and h1 inside a layer) fragment-packed
   // (common.h packed_index) for the GEMVs that read it; the input and the last layer's
   // output stay row-major, and so does every layer's output when layer_out asks for them
   const bool pkx = gemv && !layer_out && h % 128 == 0 && I % 128 == 0;
-  bool x_packed = false;  // x (this layer's input) is fragment-packed
-  long pe = -1;
   // decode: the attention output goes to the o projection's GEMV fragment-packed (also the
   // layout of an attention|o boundary record's second part)
   const bool pk_o = b->decode && gemv && !gemm_uses_tiled(M, h, H * HEAD_DIM, EPI_RESID);
   // a q/k/v|attention boundary: a pure decode call hands over the raw q/k/v rows behind x
   // (qkv_split_*); other calls hand over x and the receiver runs the whole layer
-  const bool qrec = b->decode;
-  const bool q_in = c.qkv_split_first && qrec;
-  if ((c.o_split_first || q_in) && c.n_layers > 0 && (gemv || pro.positions)) {
-    // a span starting at an o projection (or, decoding, at an attention) has no first RMSNorm
-    // launch to carry the graph's scheduler step and the SSQ slot zeroing: a small launch of
-    // its own
-    launch_step_prologue(gemv ? s->ssq : nullptr, 2 * c.n_layers, M, &pro, st);
-    pro = NormPrologue{};
+  const bool qrec = b->decode, q_in = c.qkv_split_first && qrec;
+  // decode q/k/v K-slices (reduced inside the fused attention): M <= 16 and K/32 divisible by 4 * slices
+  const int ksl = (b->decode && M <= 16 && (h / 32) % (4 * QKV_KSL) == 0) ? QKV_KSL : 1;
+  const u16* x = nullptr;  // the residual stream: the current layer's input
+  bool x_packed = false;   // x is fragment-packed
+  // the first RMSNorm launch (layer 0's input norm) also runs the embedding gather and a
+  // pending graph scheduler step (kernels.h NormPrologue): two graph nodes fewer per step
+  NormPrologue pro;
+
+  unsigned long long* slot(int i) const { return s->ssq + (size_t)i * SSQ_SLOT_WORDS; }
+  // the second part of a hand-off record, behind its [M][hidden] first part
+  u16* in_rec() const { return (u16*)x_in + (size_t)M * h; }
+  u16* out_rec() const { return (u16*)x_out + (size_t)M * h; }
+  // the span's input as its output (no layers), or as the first part of a one-layer span's record
+  int copy_input_out() {
+    if (x != (const u16*)x_out) HIP_TRY(hipMemcpyAsync(x_out, x, (size_t)M * h * 2, hipMemcpyDeviceToDevice, st));
+    return INFERD_OK;
   }
-  for (int l = 0; l < c.n_layers; ++l) {
+
+  // ---- input_layernorm -> q/k/v projection (on a q_only layer of a call that hands over x
+  // alone, only the span's first norm launch when it carries the prologue: the embedding /
+  // scheduler step).  *roped: the projection's epilogue ran QK-norm + RoPE + the cache write.
+  int qkv(int l, bool* roped) {
     const LayerW& W = s->layers[l];
-    // the residual written by this layer's last half: x_out after the span's last layer, and
-    // (row-major) the input of a last layer that ends before its o projection -- the first part
-    // of the hand-off record
-    u16* out = (l == c.n_layers - 1 && x_out) ? (u16*)x_out : s->h;
-    bool out_packed = pkx && l < c.n_layers - 1;
-    if ((c.o_split_last || c.qkv_split_last) && l == c.n_layers - 2) {
-      out = (u16*)x_out;
-      out_packed = false;
-    }
-    if (l == 0 && c.skip_first_attn) {
-      // ---- a span starting at this layer's MLP half: x is h1 (row-major, the caller's), so
-      // post_attention_layernorm runs as the span's first RMSNorm launch (slot zeroing and
-      // the graph prologue included, like layer 0's input norm)
-      pe = s->prof_begin(PROF_NORM, st);
-      launch_rmsnorm(x, h, nullptr, 0, W.post_ln, s->xn, h, M, h, c.rms_eps, st, false, gemv ? s->ssq : nullptr,
-                     2 * c.n_layers, &pro);
-      s->prof_end(pe, st);
-      const DecodeNorm dm = {DN_NONE, c.rms_eps, nullptr, nullptr};
-      const int pk =
-          (gemv && !gemm_uses_tiled(M, I, h, EPI_SILU) && !gemm_uses_tiled(M, h, I, EPI_RESID)) ? 1 : 0;
-      // a gate/up boundary (decode): columns [0, c0) of act arrived in x_in's record behind h1;
-      // this span completes the record's act in place and runs the whole down projection on it
-      const int c0 = gemv ? c.gateup_split_first : 0;
-      u16* actb = c0 ? (u16*)x_in + (size_t)M * h : s->act;
-      pe = s->prof_begin(PROF_GATEUP, st);
-      GEMM_TRY(launch_gemm(s->xn, h, W.gateup + (size_t)(c0 / 16) * (h / 32) * 512, M, I - c0, h,
-                           actb + (size_t)(c0 / 32) * 512, I, nullptr, 0, EPI_SILU, nullptr, st, &s->gws, &dm, nullptr,
-                           pk ? GEMM_PACK_C : 0, c0 ? I / 16 : 0));
-      s->prof_end(pe, st);
-      pe = s->prof_begin(PROF_DOWN, st);
-      GEMM_TRY(launch_gemm(actb, I, W.down, M, h, I, out, h, x, h, EPI_RESID, nullptr, st, &s->gws, nullptr,
-                           (gemv && l + 1 < c.n_layers) ? slot(2 * l + 1) : nullptr,
-                           (pk ? GEMM_PACK_A : 0) | (out_packed ? GEMM_PACK_C : 0)));
-      s->prof_end(pe, st);
-      x = out;
-      x_packed = out_packed;
-      if (layer_out)
-        HIP_TRY(hipMemcpyAsync((u16*)layer_out + (size_t)l * M * h, x, (size_t)M * h * 2,
-                               hipMemcpyDeviceToDevice, st));
-      LAUNCH_CHECK();
-      continue;
-    }
-    // the attention output the o projection reads: this layer's, or (a span starting at an o
-    // projection) the record's second part
-    const u16* attn_src = s->attn;
-    if (l == 0 && c.o_split_first) {  // x is the record's residual part
-      attn_src = (const u16*)x_in + (size_t)M * h;
-      goto o_proj;
-    }
-    {
-    // a q/k/v|attention boundary: q_only -- this (last) layer runs its norm and q/k/v
-    // projection only, into the record behind x (pure decode calls; other calls hand over x
-    // alone); q_recv -- this (first) layer's q/k/v rows arrive in x_in's record
+    // a q/k/v|attention boundary: q_only -- this (last) layer runs its norm and q/k/v projection
+    // only, into the record behind x (pure decode calls; other calls hand over x alone)
     const bool q_only = s->last_qkv_only(l);
-    const bool q_recv = l == 0 && q_in;
-    u16* kv_l = q_only ? nullptr : s->kv_of(l);
-    u16* q_dst = q_only ? (u16*)x_out + (size_t)M * h : nullptr;
-    // decode: QK-norm + RoPE + the cache write run inside the attention
-    const bool fused = b->decode;
-    // a span ending before this layer's o projection: the attention writes the record's second
-    // part, behind the layer's input residual (row-major; copied there when it is the span's input)
-    u16* attn_dst = s->attn;
-    if (!s->has_o(l) && !q_only) attn_dst = (u16*)x_out + (size_t)M * h;
-    // decode q/k/v K-slices (reduced inside the fused attention): M <= 16 and K/32 divisible
-    // by 4 * slices
-    int ksl = (fused && M <= 16) ? QKV_KSL : 1;
-    if ((h / 32) % (4 * ksl)) ksl = 1;
-    // ---- input_layernorm -> q/k/v projection (not on a layer whose q/k/v rows arrive in the
-    // record; on a q_only layer of a call that hands over x alone, only the span's first norm
-    // launch when it carries the prologue: the embedding / scheduler step)
     const u16* a_in = x;
-    bool qkv_done = false;
-    if (!q_recv) {
-      DecodeNorm dn = {DN_NONE, c.rms_eps, nullptr, nullptr};
-      if (gemv && l > 0) {
-        dn = {DN_EXACT, c.rms_eps, slot(2 * l - 1), W.in_ln};
-      } else if (!(q_only && !qrec && l > 0)) {
-        pe = s->prof_begin(PROF_NORM, st);
-        launch_rmsnorm(x, h, nullptr, 0, W.in_ln, s->xn, h, M, h, c.rms_eps, st, false, gemv ? s->ssq : nullptr,
-                       2 * c.n_layers, l == 0 ? &pro : nullptr);
-        s->prof_end(pe, st);
-        a_in = s->xn;
-      }
-      if (!(q_only && !qrec)) {
-        pe = s->prof_begin(PROF_QKV, st);
-        // prefill: q/k norm + RoPE and the K/V cache write in the projection's epilogue when
-        // the persistent GEMM runs it (else the separate qk_norm_rope_kv launch below)
-        if (ksl > 1) {
-          launch_gemm_decode_partial(a_in, h, W.qkv, M, qkvN, h, ksl, s->qkv_part, dn, st,
-                                     (x_packed && a_in == x) ? GEMM_PACK_A : 0);
-          // the record's q/k/v rows: the slices summed as the fused attention sums them
-          if (q_only) launch_qkv_reduce(s->qkv_part, ksl, M, qkvN, q_dst, st);
-        } else {
-          if (!b->decode && !q_only) {
-            const QkvEpilogue qe = {b->positions, b->slots, W.q_norm, W.k_norm, s->cos_t, s->sin_t, s->q, kv_l,
-                                    H, KV, c.rms_eps};
-            qkv_done = launch_gemm_qkv_fused(a_in, h, W.qkv, M, qkvN, h, qe, st);
-          }
-          if (!qkv_done)
-            GEMM_TRY(launch_gemm(a_in, h, W.qkv, M, qkvN, h, q_only ? q_dst : s->qkv, qkvN, nullptr, 0, EPI_NONE,
-                                 nullptr, st, &s->gws, &dn, nullptr, (x_packed && a_in == x) ? GEMM_PACK_A : 0));
-        }
-        s->prof_end(pe, st);
-      }
-    }
-    if (q_only) {  // the record: x (first part; the span's input copied there), q/k/v rows
-      if (c.n_layers == 1 && x != (const u16*)x_out)
-        HIP_TRY(hipMemcpyAsync(x_out, x, (size_t)M * h * 2, hipMemcpyDeviceToDevice, st));
-      LAUNCH_CHECK();
-      continue;
-    }
-    if (fused) {  // QK-norm + RoPE + cache write inside attention
-      pe = s->prof_begin(PROF_ATTN, st);
-      if (q_recv)
-        launch_attn_decode_fused((const u16*)x_in + (size_t)M * h, qkvN, W.q_norm, W.k_norm, s->cos_t, s->sin_t,
-                                 c.rms_eps, kv_l, ab, H, KV, scale, attn_dst, s->attn_ws, st, nullptr, 0, pk_o);
-      else if (ksl > 1)
-        launch_attn_decode_fused(nullptr, qkvN, W.q_norm, W.k_norm, s->cos_t, s->sin_t, c.rms_eps, kv_l, ab, H, KV,
-                                 scale, attn_dst, s->attn_ws, st, s->qkv_part, ksl, pk_o);
-      else
-        launch_attn_decode_fused(s->qkv, qkvN, W.q_norm, W.k_norm, s->cos_t, s->sin_t, c.rms_eps, kv_l, ab, H, KV,
-                                 scale, attn_dst, s->attn_ws, st, nullptr, 0, pk_o);
+    DecodeNorm dn = {DN_NONE, c.rms_eps, nullptr, nullptr};
+    if (gemv && l > 0) {
+      dn = {DN_EXACT, c.rms_eps, slot(2 * l - 1), W.in_ln};
+    } else if (!(q_only && !qrec && l > 0)) {
+      const long pe = s->prof_begin(PROF_NORM, st);
+      launch_rmsnorm(x, h, nullptr, 0, W.in_ln, s->xn, h, M, h, c.rms_eps, st, false, gemv ? s->ssq : nullptr,
+                     2 * c.n_layers, l == 0 ? &pro : nullptr);
       s->prof_end(pe, st);
+      a_in = s->xn;
+    }
+    if (q_only && !qrec) return INFERD_OK;
+    const long pe = s->prof_begin(PROF_QKV, st);
+    // prefill: q/k norm + RoPE and the K/V cache write in the projection's epilogue when
+    // the persistent GEMM runs it (else the separate qk_norm_rope_kv launch in attention())
+    if (ksl > 1) {
+      launch_gemm_decode_partial(a_in, h, W.qkv, M, qkvN, h, ksl, s->qkv_part, dn, st,
+                                 (x_packed && a_in == x) ? GEMM_PACK_A : 0);
+      // the record's q/k/v rows: the slices summed as the fused attention sums them
+      if (q_only) launch_qkv_reduce(s->qkv_part, ksl, M, qkvN, out_rec(), st);
     } else {
-      if (!qkv_done) {
-        pe = s->prof_begin(PROF_ROPE, st);
-        launch_qk_norm_rope_kv(s->qkv, qkvN, b->positions, b->slots, W.q_norm, W.k_norm, s->cos_t, s->sin_t, s->q,
-                               kv_l, M, H, KV, c.rms_eps, st);
-        s->prof_end(pe, st);
+      if (!b->decode && !q_only) {
+        const QkvEpilogue qe = {b->positions, b->slots, W.q_norm, W.k_norm, s->cos_t, s->sin_t, s->q, s->kv_of(l),
+                                H, KV, c.rms_eps};
+        *roped = launch_gemm_qkv_fused(a_in, h, W.qkv, M, qkvN, h, qe, st);
       }
-      pe = s->prof_begin(PROF_ATTN, st);
-      launch_attn_prefill(s->q, kv_l, ab, H, KV, scale, attn_dst, st);
+      if (!*roped)
+        GEMM_TRY(launch_gemm(a_in, h, W.qkv, M, qkvN, h, q_only ? out_rec() : s->qkv, qkvN, nullptr, 0, EPI_NONE,
+                             nullptr, st, &s->gws, &dn, nullptr, (x_packed && a_in == x) ? GEMM_PACK_A : 0));
+    }
+    s->prof_end(pe, st);
+    return INFERD_OK;
+  }
+
+  // ---- attention into dst.  q_recv: this (first) layer's q/k/v rows arrive in x_in's record
+  int attention(int l, bool q_recv, bool roped, u16* dst) {
+    const LayerW& W = s->layers[l];
+    u16* kv_l = s->kv_of(l);
+    if (!b->decode && !roped) {
+      const long pe = s->prof_begin(PROF_ROPE, st);
+      launch_qk_norm_rope_kv(s->qkv, qkvN, b->positions, b->slots, W.q_norm, W.k_norm, s->cos_t, s->sin_t, s->q,
+                             kv_l, M, H, KV, c.rms_eps, st);
       s->prof_end(pe, st);
     }
-    if (!s->has_o(l)) {  // the record: x (first part; the span's input copied there), attention output
-      if (c.n_layers == 1 && x != (const u16*)x_out)
-        HIP_TRY(hipMemcpyAsync(x_out, x, (size_t)M * h * 2, hipMemcpyDeviceToDevice, st));
-      LAUNCH_CHECK();
-      continue;
-    }
-    }
-  o_proj:
-    // ---- h1 = x + o_proj(attn)   (in place when x == s->h: same-element read-then-write)
-    // h1 is packed iff pkx.  An in-place epilogue needs one layout on both sides, so h1 goes
-    // to s->xn (free after the q/k/v projection) where s->h holds a row-major x (the first
-    // span's embedding output) or is to receive this layer's row-major output (the last layer
-    // without x_out).
-    u16* h1 = (pkx && ((x == s->h && !x_packed) || (out == s->h && !out_packed))) ? s->xn : s->h;
-    bool h1_packed = pkx;
-    if (!s->has_mlp(l)) {
-      // a span ending at this layer's attention half: h1 is the span's (row-major) output;
-      // without x_out it goes to s->xn (free after the q/k/v projection), never in place over
-      // a packed x
-      h1 = x_out ? (u16*)x_out : s->xn;
-      h1_packed = false;
-      if (gemv && c.gateup_split_last && !x_out)
-        return fail(INFERD_ERR_ARG, "a span ending inside a gate/up projection needs x_out (the hand-off record)");
-    }
-    pe = s->prof_begin(PROF_O, st);
-    GEMM_TRY(launch_gemm(attn_src, H * HEAD_DIM, W.o, M, h, H * HEAD_DIM, h1, h, x, h, EPI_RESID, nullptr, st, &s->gws, nullptr,
-                gemv ? slot(2 * l) : nullptr,
-                (pk_o ? GEMM_PACK_A : 0) | (x_packed ? GEMM_PACK_R : 0) | (h1_packed ? GEMM_PACK_C : 0)));
+    // decode: QK-norm + RoPE + cache write inside attention, on the record's q/k/v rows, the
+    // projection's K-slices (part) or the projection's rows
+    const u16* rows = q_recv ? in_rec() : (ksl > 1 ? nullptr : s->qkv);
+    const float* part = (!q_recv && ksl > 1) ? s->qkv_part : nullptr;
+    const long pe = s->prof_begin(PROF_ATTN, st);
+    if (b->decode)
+      launch_attn_decode_fused(rows, qkvN, W.q_norm, W.k_norm, s->cos_t, s->sin_t, c.rms_eps, kv_l, ab, H, KV, scale,
+                               dst, s->attn_ws, st, part, part ? ksl : 0, pk_o);
+    else
+      launch_attn_prefill(s->q, kv_l, ab, H, KV, scale, dst, st);
     s->prof_end(pe, st);
-    if (!s->has_mlp(l)) {
-      const int c1 = gemv ? c.gateup_split_last : 0;
-      if (c1) {
-        // a gate/up boundary (decode): act columns [0, c1) go into x_out's record behind h1,
-        // normed from the SSQ slot this layer's o GEMV just filled (the record's act is
-        // fragment-packed with the whole projection's row length, as the receiver reads it)
-        const DecodeNorm dm = {DN_EXACT, c.rms_eps, slot(2 * l), W.post_ln};
-        pe = s->prof_begin(PROF_GATEUP, st);
-        GEMM_TRY(launch_gemm(h1, h, W.gateup, M, c1, h, h1 + (size_t)M * h, I, nullptr, 0, EPI_SILU, nullptr, st,
-                             &s->gws, &dm, nullptr, GEMM_PACK_C, I / 16));
-        s->prof_end(pe, st);
-      }
-      x = h1;
-      x_packed = false;
-      if (layer_out)
-        HIP_TRY(hipMemcpyAsync((u16*)layer_out + (size_t)l * M * h, x, (size_t)M * h * 2,
-                               hipMemcpyDeviceToDevice, st));
-      LAUNCH_CHECK();
-      continue;
-    }
-    // ---- post_attention_layernorm -> gate/up (+SwiGLU)
-    const u16* m_in = h1;
+    return INFERD_OK;
+  }
+
+  // ---- h1 = x + o_proj(attn)   (in place when x == s->h: same-element read-then-write)
+  int o_proj(int l, const u16* attn_src, u16* h1, bool h1_packed) {
+    const long pe = s->prof_begin(PROF_O, st);
+    GEMM_TRY(launch_gemm(attn_src, H * HEAD_DIM, s->layers[l].o, M, h, H * HEAD_DIM, h1, h, x, h, EPI_RESID, nullptr, st,
+                         &s->gws, nullptr, gemv ? slot(2 * l) : nullptr,
+                         (pk_o ? GEMM_PACK_A : 0) | (x_packed ? GEMM_PACK_R : 0) | (h1_packed ? GEMM_PACK_C : 0)));
+    s->prof_end(pe, st);
+    return INFERD_OK;
+  }
+
+  // ---- post_attention_layernorm -> gate/up (+SwiGLU) into actb -> out = r + down(actb), r being h1.
+  // A gate/up boundary's receiver: columns [0, c0) of actb (the record's act) arrived with x_in.
+  int mlp(int l, const u16* r, bool r_packed, int c0, u16* actb, u16* out, bool out_packed) {
+    const LayerW& W = s->layers[l];
+    // a span starting at this layer's MLP half: r is the caller's row-major h1, and
+    // post_attention_layernorm runs as the span's first RMSNorm launch (slot zeroing and the
+    // graph prologue included, like layer 0's input norm)
+    const bool first = s->mlp_only(l);
+    const u16* m_in = r;
     DecodeNorm dm = {DN_NONE, c.rms_eps, nullptr, nullptr};
-    if (gemv) {
+    if (gemv && !first) {
       dm = {DN_EXACT, c.rms_eps, slot(2 * l), W.post_ln};
     } else {
-      pe = s->prof_begin(PROF_NORM, st);
-      launch_rmsnorm(h1, h, nullptr, 0, W.post_ln, s->xn, h, M, h, c.rms_eps, st);
+      const long pe = s->prof_begin(PROF_NORM, st);
+      launch_rmsnorm(r, h, nullptr, 0, W.post_ln, s->xn, h, M, h, c.rms_eps, st, false,
+                     (first && gemv) ? s->ssq : nullptr, first ? 2 * c.n_layers : 0, first ? &pro : nullptr);
       s->prof_end(pe, st);
       m_in = s->xn;
     }
-    pe = s->prof_begin(PROF_GATEUP, st);
+    long pe = s->prof_begin(PROF_GATEUP, st);
     // decode (the GEMV path): act goes between gate/up and down fragment-packed
-    const int pk =
-        (gemv && !gemm_uses_tiled(M, I, h, EPI_SILU) && !gemm_uses_tiled(M, h, I, EPI_RESID)) ? 1 : 0;
-    GEMM_TRY(launch_gemm(m_in, h, W.gateup, M, I, h, s->act, I, nullptr, 0, EPI_SILU, nullptr, st, &s->gws, &dm, nullptr,
-                (pk ? GEMM_PACK_C : 0) | ((pkx && m_in == h1) ? GEMM_PACK_A : 0)));
+    const int pk = (gemv && !gemm_uses_tiled(M, I, h, EPI_SILU) && !gemm_uses_tiled(M, h, I, EPI_RESID)) ? 1 : 0;
+    GEMM_TRY(launch_gemm(m_in, h, W.gateup + (size_t)(c0 / 16) * (h / 32) * 512, M, I - c0, h,
+                         actb + (size_t)(c0 / 32) * 512, I, nullptr, 0, EPI_SILU, nullptr, st, &s->gws, &dm, nullptr,
+                         (pk ? GEMM_PACK_C : 0) | ((r_packed && m_in == r) ? GEMM_PACK_A : 0), c0 ? I / 16 : 0));
     s->prof_end(pe, st);
-    // ---- x = h1 + down(act)
     pe = s->prof_begin(PROF_DOWN, st);
-    GEMM_TRY(launch_gemm(s->act, I, W.down, M, h, I, out, h, h1, h, EPI_RESID, nullptr, st, &s->gws, nullptr,
-                (gemv && l + 1 < c.n_layers) ? slot(2 * l + 1) : nullptr,
-                (pk ? GEMM_PACK_A : 0) | (pkx ? GEMM_PACK_R : 0) | (out_packed ? GEMM_PACK_C : 0)));
+    GEMM_TRY(launch_gemm(actb, I, W.down, M, h, I, out, h, r, h, EPI_RESID, nullptr, st, &s->gws, nullptr,
+                         (gemv && l + 1 < c.n_layers) ? slot(2 * l + 1) : nullptr,
+                         (pk ? GEMM_PACK_A : 0) | (r_packed ? GEMM_PACK_R : 0) | (out_packed ? GEMM_PACK_C : 0)));
     s->prof_end(pe, st);
+    return INFERD_OK;
+  }
+
+  // a gate/up boundary (decode): act columns [0, c1) go into x_out's record behind h1,
+  // normed from the SSQ slot this layer's o GEMV just filled (the record's act is
+  // fragment-packed with the whole projection's row length, as the receiver reads it)
+  int gateup_prefix(int l, u16* h1, int c1) {
+    const DecodeNorm dm = {DN_EXACT, c.rms_eps, slot(2 * l), s->layers[l].post_ln};
+    const long pe = s->prof_begin(PROF_GATEUP, st);
+    GEMM_TRY(launch_gemm(h1, h, s->layers[l].gateup, M, c1, h, h1 + (size_t)M * h, I, nullptr, 0, EPI_SILU, nullptr, st,
+                         &s->gws, &dm, nullptr, GEMM_PACK_C, I / 16));
+    s->prof_end(pe, st);
+    return INFERD_OK;
+  }
+
+  // the layer's output (packed iff `packed`) becomes the next layer's input
+  int end_layer(int l, const u16* out, bool packed) {
     x = out;
-    x_packed = out_packed;
+    x_packed = packed;
     if (layer_out)
-      HIP_TRY(hipMemcpyAsync((u16*)layer_out + (size_t)l * M * h, x, (size_t)M * h * 2,
-                             hipMemcpyDeviceToDevice, st));
+      HIP_TRY(hipMemcpyAsync((u16*)layer_out + (size_t)l * M * h, x, (size_t)M * h * 2, hipMemcpyDeviceToDevice, st));
     LAUNCH_CHECK();
+    return INFERD_OK;
   }
-  if (c.has_lm_head && (next_ids || logits)) {
-    if (B > 64) return fail(INFERD_ERR_ARG, "lm_head argmax supports <= 64 sequences per call");
-    // last row of each sequence: seq_start[b+1] - 1
-    pe = s->prof_begin(PROF_LMHEAD, st);
-    // the final norm writes the last rows fragment-packed for the lm_head GEMV (its A operand
-    // only; the logits it may also store stay row-major).  Folding this norm into the GEMV's A
-    // path (DN_EXACT, as q/k/v) measured 213.8 us in the graph against 195 + 5 us (round 3).
-    const bool pk_last = h % 32 == 0;
-    launch_rmsnorm(x, h, b->seq_start + 1, 1, s->final_norm, s->last, h, B, h, c.rms_eps, st, pk_last);
-    // a sampled head reads the logits of the tiles its keys select: they go to the span's own
-    // buffer when the caller wants none
-    const bool draw = s->sampling_on && next_ids;
-    u16* lg = (draw && !logits) ? s->sample_logits : (u16*)logits;
-    GEMM_TRY(launch_gemm(s->last, h, s->lm_head, B, c.vocab, h, lg, c.vocab, nullptr, 0, EPI_ARGMAX,
-                s->argmax_partial, st, nullptr, nullptr, nullptr, pk_last ? GEMM_PACK_A : 0));
-    if (draw)
-      launch_sample(lg, B, c.vocab, s->argmax_partial, s->sampling.temperature, s->sampling.top_k, s->sampling.top_p,
-                    s->sampling.seed, s->sampling.row_seeds, b->ctx_lens, next_ids, nullptr, s->err, st);
-    else if (next_ids)
-      launch_argmax_reduce(s->argmax_partial, c.vocab / 16, B, next_ids, st);
-    s->prof_end(pe, st);
+
+  int head(int32_t* next_ids, void* logits) {
+    if (c.has_lm_head && (next_ids || logits)) {
+      // last row of each sequence: seq_start[b+1] - 1
+      const long pe = s->prof_begin(PROF_LMHEAD, st);
+      // the final norm writes the last rows fragment-packed for the lm_head GEMV (its A operand
+      // only; the logits it may also store stay row-major).  Folding this norm into the GEMV's A
+      // path (DN_EXACT, as q/k/v) measured 213.8 us in the graph against 195 + 5 us (round 3).
+      const bool pk_last = h % 32 == 0;
+      launch_rmsnorm(x, h, b->seq_start + 1, 1, s->final_norm, s->last, h, B, h, c.rms_eps, st, pk_last);
+      // a sampled head reads the logits of the tiles its keys select: they go to the span's own
+      // buffer when the caller wants none
+      const bool draw = s->sampling_on && next_ids;
+      u16* lg = (draw && !logits) ? s->sample_logits : (u16*)logits;
+      GEMM_TRY(launch_gemm(s->last, h, s->lm_head, B, c.vocab, h, lg, c.vocab, nullptr, 0, EPI_ARGMAX,
+                           s->argmax_partial, st, nullptr, nullptr, nullptr, pk_last ? GEMM_PACK_A : 0));
+      if (draw)
+        launch_sample(lg, B, c.vocab, s->argmax_partial, s->sampling.temperature, s->sampling.top_k,
+                      s->sampling.top_p, s->sampling.seed, s->sampling.row_seeds, b->ctx_lens, next_ids, nullptr,
+                      s->err, st);
+      else if (next_ids)
+        launch_argmax_reduce(s->argmax_partial, c.vocab / 16, B, next_ids, st);
+      s->prof_end(pe, st);
+    }
+    if (normed_out) {
+      // vocab-parallel head: the last row of each sequence, final-normed and fragment-packed (the
+      // A operand of every stage's inferd_span_head_shard), handed over instead of running lm_head
+      const long pe = s->prof_begin(PROF_NORM, st);
+      launch_rmsnorm(x, h, b->seq_start + 1, 1, s->final_norm, (u16*)normed_out, h, B, h, c.rms_eps, st, true);
+      s->prof_end(pe, st);
+    }
+    LAUNCH_CHECK();
+    return INFERD_OK;
   }
-  if (normed_out) {
-    // vocab-parallel head: the last row of each sequence, final-normed and fragment-packed (the
-    // A operand of every stage's inferd_span_head_shard), handed over instead of running lm_head
-    pe = s->prof_begin(PROF_NORM, st);
-    launch_rmsnorm(x, h, b->seq_start + 1, 1, s->final_norm, (u16*)normed_out, h, B, h, c.rms_eps, st, true);
-    s->prof_end(pe, st);
+
+  // adv: the graph scheduler step the call's first launch runs (step_body), or null
+  int run(const int32_t* ids, int32_t* next_ids, void* logits, const NormPrologue* adv) {
+    if (normed_out && B > 64) return fail(INFERD_ERR_ARG, "final_norm_out supports <= 64 sequences per call");
+    if (gemv && c.gateup_split_first && !x_in)
+      return fail(INFERD_ERR_ARG, "a span starting inside a gate/up projection needs x_in (the hand-off record)");
+    if ((c.o_split_last || c.qkv_split_last) && !x_out)
+      return fail(INFERD_ERR_ARG, "a span ending before an o projection or an attention needs x_out (the hand-off record)");
+    if (s->sampling_on && next_ids && logits && (uintptr_t)logits % 16)
+      return fail(INFERD_ERR_ARG, "a sampled head reads `logits` back: it must be 16-byte aligned");
+    if (c.has_embed && !ids) return fail(INFERD_ERR_ARG, "first span needs token ids");
+    if (!c.has_embed && !x_in) return fail(INFERD_ERR_ARG, "span needs x_in hidden states");
+    if (gemv && c.n_layers > 0 && !s->has_mlp(c.n_layers - 1) && c.gateup_split_last && !x_out)
+      return fail(INFERD_ERR_ARG, "a span ending inside a gate/up projection needs x_out (the hand-off record)");
+    if (c.has_lm_head && (next_ids || logits) && B > 64)
+      return fail(INFERD_ERR_ARG, "lm_head argmax supports <= 64 sequences per call");
+    // ---- the arguments hold: from here on, launches
+    if (adv) pro = *adv;
+    x = c.has_embed ? s->h : (const u16*)x_in;
+    if (c.has_embed && c.n_layers > 0) {
+      pro.ids = ids;
+      pro.table = s->embed;
+      pro.vocab = c.vocab;
+      pro.err = s->err;
+      pro.x_out = s->h;
+    } else if (c.has_embed) {
+      launch_embed(ids, s->embed, M, h, c.vocab, s->h, s->err, st);
+    }
+    int rc = INFERD_OK;
+    if (c.n_layers == 0 && x_out && (rc = copy_input_out())) return rc;
+    if ((c.o_split_first || q_in) && c.n_layers > 0 && (gemv || pro.positions)) {
+      // a span starting at an o projection (or, decoding, at an attention) has no first RMSNorm
+      // launch to carry the graph's scheduler step and the SSQ slot zeroing: a small launch of
+      // its own
+      launch_step_prologue(gemv ? s->ssq : nullptr, 2 * c.n_layers, M, &pro, st);
+      pro = NormPrologue{};
+    }
+    for (int l = 0; l < c.n_layers; ++l) {
+      // the residual written by this layer's last half: x_out after the span's last layer, and
+      // (row-major) the input of a last layer that ends before its o projection -- the first part
+      // of the hand-off record
+      u16* out = (l == c.n_layers - 1 && x_out) ? (u16*)x_out : s->h;
+      bool out_packed = pkx && l < c.n_layers - 1;
+      if ((c.o_split_last || c.qkv_split_last) && l == c.n_layers - 2) {
+        out = (u16*)x_out;
+        out_packed = false;
+      }
+      const bool q_recv = s->qkv_in_record(l, b->decode);
+      bool roped = false;
+      if (s->has_qkv(l) && !q_recv && (rc = qkv(l, &roped))) return rc;
+      // a span ending before this layer's o projection: the attention writes the record's second
+      // part, behind the layer's input residual (row-major; copied there when it is the span's input)
+      if (s->has_attn(l) && (rc = attention(l, q_recv, roped, s->has_o(l) ? s->attn : out_rec()))) return rc;
+      if (s->ends_in_record(l)) {  // the record: x (first part; the span's input copied there), q/k/v or attention
+        if (c.n_layers == 1 && (rc = copy_input_out())) return rc;
+        LAUNCH_CHECK();
+        continue;
+      }
+      // the residual the MLP half adds to: h1, or x where the span starts at this MLP half
+      const u16* r = x;
+      bool r_packed = x_packed;
+      u16* h1 = nullptr;
+      if (s->has_o(l)) {
+        // h1 is packed iff pkx.  An in-place epilogue needs one layout on both sides, so h1 goes
+        // to s->xn (free after the q/k/v projection) where s->h holds a row-major x (the first
+        // span's embedding output) or is to receive this layer's row-major output (the last layer
+        // without x_out).
+        h1 = (pkx && ((x == s->h && !x_packed) || (out == s->h && !out_packed))) ? s->xn : s->h;
+        bool h1_packed = pkx;
+        if (!s->has_mlp(l)) {
+          // a span ending at this layer's attention half: h1 is the span's (row-major) output;
+          // without x_out it goes to s->xn (free after the q/k/v projection), never in place over
+          // a packed x
+          h1 = x_out ? (u16*)x_out : s->xn;
+          h1_packed = false;
+        }
+        // the attention output the o projection reads: this layer's, or (a span starting at an o
+        // projection; x is the record's residual part) the record's second part
+        if ((rc = o_proj(l, s->has_attn(l) ? s->attn : in_rec(), h1, h1_packed))) return rc;
+        r = h1;
+        r_packed = h1_packed;
+      }
+      if (s->has_mlp(l)) {
+        // a gate/up boundary (decode): columns [0, c0) of act arrived in x_in's record behind h1;
+        // this span completes the record's act in place
+        const int c0 = (gemv && s->mlp_only(l)) ? c.gateup_split_first : 0;
+        if ((rc = mlp(l, r, r_packed, c0, c0 ? in_rec() : s->act, out, out_packed))) return rc;
+        rc = end_layer(l, out, out_packed);
+      } else {
+        const int c1 = gemv ? c.gateup_split_last : 0;
+        if (c1 && (rc = gateup_prefix(l, h1, c1))) return rc;
+        rc = end_layer(l, h1, false);
+      }
+      if (rc) return rc;
+    }
+    return head(next_ids, logits);
   }
-  LAUNCH_CHECK();
-  return INFERD_OK;
+};
+
+int forward_impl(InferdSpan* s, const InferdBatch* b, const int32_t* ids, const void* x_in, void* x_out,
+                 int32_t* next_ids, void* logits, void* layer_out, hipStream_t st, const NormPrologue* adv) {
+  if (!s) return fail(INFERD_ERR_ARG, "null span");
+  if (int rc = check_batch(s, b)) return rc;
+  Forward f{s, b, x_in, s->cfg.final_norm_out ? nullptr : x_out, s->cfg.final_norm_out ? x_out : nullptr, layer_out, st};
+  return f.run(ids, next_ids, logits, adv);
+}
+}  // namespace
+
+extern "C" int inferd_span_forward(InferdSpan* s, const InferdBatch* b, const int32_t* ids,
+                                   const void* x_in, void* x_out, int32_t* next_ids, void* logits,
+                                   void* layer_out, void* stream) {
+  return forward_impl(s, b, ids, x_in, x_out, next_ids, logits, layer_out, (hipStream_t)stream, nullptr);
 }
 
 // Vocab-parallel lm_head shard: the greedy key of each row over this span's lm_head rows
@@ -950,23 +952,21 @@ namespace {
 // the scheduler step of a decode replay (advance) + the forward, on `st` (captured or eager)
 int step_body(InferdSpan* s, const InferdBatch* b, int32_t advance, const int32_t* ids, const void* x_in, void* x_out,
               int32_t* next_ids, void* logits, hipStream_t st) {
-  if (advance && s->cfg.n_layers > 0) {  // run by layer 0's input norm (NormPrologue)
-    s->adv = NormPrologue{};
-    s->adv.positions = (int32_t*)b->positions;
-    s->adv.slots = (int32_t*)b->slots;
-    s->adv.ctx_lens = (int32_t*)b->ctx_lens;
-    s->adv.block_table = b->block_table;
-    s->adv.max_pages = b->max_pages;
-    s->adv.B = b->n_seqs;
-    s->adv.err = s->err;
-    s->adv_pending = true;
+  NormPrologue adv;
+  const bool in_norm = advance && s->cfg.n_layers > 0;
+  if (in_norm) {  // run by the forward's first launch (layer 0's input norm: NormPrologue)
+    adv.positions = (int32_t*)b->positions;
+    adv.slots = (int32_t*)b->slots;
+    adv.ctx_lens = (int32_t*)b->ctx_lens;
+    adv.block_table = b->block_table;
+    adv.max_pages = b->max_pages;
+    adv.B = b->n_seqs;
+    adv.err = s->err;
   } else if (advance) {
     launch_decode_advance((int32_t*)b->positions, (int32_t*)b->slots, (int32_t*)b->ctx_lens, b->block_table,
                           b->max_pages, b->n_seqs, s->err, st);
   }
-  const int rc = inferd_span_forward(s, b, ids, x_in, x_out, next_ids, logits, nullptr, st);
-  s->adv_pending = false;
-  return rc;
+  return forward_impl(s, b, ids, x_in, x_out, next_ids, logits, nullptr, st, in_norm ? &adv : nullptr);
 }
 }  // namespace
 

@@ -440,6 +440,146 @@ def test_o_boundary_chain_bit_exact(split, T):
         s.check_errors()
 
 
+@pytest.mark.parametrize("T", [9, (30, 9, 17)], ids=["prefill_small", "ragged"])
+@pytest.mark.parametrize("split,first", [("o", False), ("q", False), ("q", True), ("o", True)],
+                         ids=["o_middle", "q_middle", "q_first", "o_first"])
+def test_one_layer_record_span_chain_bit_exact(split, first, T):
+    """One-layer spans that end at a record boundary: the record's first part is the span's own
+    input, copied there -- the caller's x_in ("middle": Qwen3-0.6B layers 0..3 as [0], [1..1q] or
+    [1..1v], [1o..3] or [1k..3] with lm_head) or the span's embedding output ("first": [0..0q] or
+    [0..0v] with the embedding, [0o..1] or [0k..1], [2..3]).  Each chain gives bit-identical logits and ids to one
+    span over the four layers, at the prefill of 3 sequences and at each of 5 decode-graph steps
+    with forced ids."""
+    from inferd_amd.pipeline import StageRange, buffer_elems
+    from inferd_amd.runtime import DecodeGraph
+    d = R.CONFIGS["qwen3-0.6b"]
+    B, STEPS = 3, 5
+    gen = torch.Generator().manual_seed(47)
+    lens = T if isinstance(T, tuple) else (T,) * B
+    N = sum(lens)
+    ids = torch.randint(0, d.vocab, (N,), generator=gen)
+    forced = torch.randint(0, d.vocab, (STEPS, B), generator=gen)
+    o, q = split == "o", split == "q"
+    if first:
+        ranges = [StageRange(0, 1, last_o=o, last_q=q), StageRange(0, 4, first_o=o, first_q=q), StageRange(4, 4)]
+    else:
+        ranges = [StageRange(0, 2), StageRange(2, 1, last_o=o, last_q=q), StageRange(2, 6, first_o=o, first_q=q)]
+    assert ranges[0 if first else 1].n_layers == 1
+    chain = [span("qwen3-0.6b", r.first_layer, r.n_layers, i == 0, i == 2, kv_pages=16, max_tokens=N + 64,
+                  max_seqs=B, max_positions=1024, **r.span_kwargs()) for i, r in enumerate(ranges)]
+    one = span("qwen3-0.6b", 0, 4, True, True, kv_pages=16, max_tokens=N + 64, max_seqs=B, max_positions=1024)
+    sess = [f"r{b}" for b in range(B)]
+    reqs = [(sid, n) for sid, n in zip(sess, lens)]
+    o0 = chain[0].forward(reqs, ids=ids)
+    o1 = chain[1].forward(reqs, x=o0.get("record", o0["hidden"]))
+    oc = chain[2].forward(reqs, x=o1.get("record", o1["hidden"]), want_logits=True, want_next_ids=True,
+                          want_hidden=False)
+    oo = one.forward(reqs, ids=ids, want_logits=True, want_next_ids=True, want_hidden=False)
+    assert torch.equal(oc["logits"], oo["logits"]), (oc["logits"].float() - oo["logits"].float()).abs().max()
+    assert torch.equal(oc["next_ids"], oo["next_ids"])
+    ids_c = torch.zeros(B, dtype=torch.int32, device=DEV)
+    ids_o = torch.zeros(B, dtype=torch.int32, device=DEV)
+    recs = [torch.zeros(buffer_elems(d, B, r.last_col, r.last_o, True, r.last_q), dtype=torch.bfloat16, device=DEV)
+            for r in ranges[:2]]
+    lg_c = torch.zeros(B, d.vocab, dtype=torch.bfloat16, device=DEV)
+    lg_o = torch.zeros(B, d.vocab, dtype=torch.bfloat16, device=DEV)
+    nid_c = torch.zeros(B, dtype=torch.int32, device=DEV)
+    nid_o = torch.zeros(B, dtype=torch.int32, device=DEV)
+    graphs = [DecodeGraph(chain[0], sess, STEPS, ids=ids_c, hidden_out=recs[0]),
+              DecodeGraph(chain[1], sess, STEPS, x=recs[0], hidden_out=recs[1]),
+              DecodeGraph(chain[2], sess, STEPS, x=recs[1], next_ids=nid_c, logits=lg_c)]
+    g1 = DecodeGraph(one, sess, STEPS, ids=ids_o, next_ids=nid_o, logits=lg_o)
+    for k in range(STEPS):
+        ids_c.copy_(forced[k])
+        ids_o.copy_(forced[k])
+        for g in graphs:
+            g.launch()
+        g1.launch()
+        assert torch.equal(lg_c, lg_o), (k, (lg_c.float() - lg_o.float()).abs().max())
+        assert torch.equal(nid_c, nid_o), k
+    for s in chain + [one]:
+        s.check_errors()
+
+
+# Launches per kernel class (ops.PROF_CLASSES order: rmsnorm, q/k/v, qk-norm + rope + kv write,
+# attention, o, gate/up, down, lm_head) of one forward of a 3-layer span, by span kind and call
+# shape.  How to read a row: a call of <= 64 rows ("decode", "prefill9") launches one RMSNorm, the
+# span's first (every later norm is folded into the GEMV that reads it), and none where the span
+# starts at an o projection or at an attention; a larger call ("prefill70") launches one per norm
+# the span owns.  Only a pure decode call runs qk-norm + rope inside the attention (column 3 = 0).
+# A layer cut by a boundary contributes the parts on the span's side of it; a gate/up boundary's
+# sender adds the gate/up prefix launch in calls of <= 64 rows; a q/k/v|attention boundary moves
+# the q/k/v projection across in pure decode calls only -- other calls hand over x, so the sender's
+# last layer launches nothing and the receiver runs the whole layer.
+SPAN_LAUNCHES = {
+    "plain": ({}, {"decode": (1, 3, 0, 3, 3, 3, 3, 1), "prefill9": (1, 3, 3, 3, 3, 3, 3, 1),
+                   "prefill70": (6, 3, 3, 3, 3, 3, 3, 1)}),
+    "skip_first_attn": ({"skip_first_attn": True},
+                        {"decode": (1, 2, 0, 2, 2, 3, 3, 0), "prefill9": (1, 2, 2, 2, 2, 3, 3, 0),
+                         "prefill70": (5, 2, 2, 2, 2, 3, 3, 0)}),
+    "skip_last_mlp": ({"skip_last_mlp": True},
+                      {"decode": (1, 3, 0, 3, 3, 2, 2, 0), "prefill9": (1, 3, 3, 3, 3, 2, 2, 0),
+                       "prefill70": (5, 3, 3, 3, 3, 2, 2, 0)}),
+    "gateup_split_first": ({"skip_first_attn": True, "gateup_split_first": 1024},
+                           {"decode": (1, 2, 0, 2, 2, 3, 3, 0), "prefill9": (1, 2, 2, 2, 2, 3, 3, 0),
+                            "prefill70": (5, 2, 2, 2, 2, 3, 3, 0)}),
+    "gateup_split_last": ({"skip_last_mlp": True, "gateup_split_last": 1024},
+                          {"decode": (1, 3, 0, 3, 3, 3, 2, 0), "prefill9": (1, 3, 3, 3, 3, 3, 2, 0),
+                           "prefill70": (5, 3, 3, 3, 3, 2, 2, 0)}),
+    "o_split_first": ({"o_split_first": True},
+                      {"decode": (0, 2, 0, 2, 3, 3, 3, 0), "prefill9": (0, 2, 2, 2, 3, 3, 3, 0),
+                       "prefill70": (5, 2, 2, 2, 3, 3, 3, 0)}),
+    "o_split_last": ({"o_split_last": True},
+                     {"decode": (1, 3, 0, 3, 2, 2, 2, 0), "prefill9": (1, 3, 3, 3, 2, 2, 2, 0),
+                      "prefill70": (5, 3, 3, 3, 2, 2, 2, 0)}),
+    "qkv_split_first": ({"qkv_split_first": True},
+                        {"decode": (0, 2, 0, 3, 3, 3, 3, 0), "prefill9": (1, 3, 3, 3, 3, 3, 3, 0),
+                         "prefill70": (6, 3, 3, 3, 3, 3, 3, 0)}),
+    "qkv_split_last": ({"qkv_split_last": True},
+                       {"decode": (1, 3, 0, 2, 2, 2, 2, 0), "prefill9": (1, 2, 2, 2, 2, 2, 2, 0),
+                        "prefill70": (4, 2, 2, 2, 2, 2, 2, 0)}),
+    "one_layer_o_split_last": ({"o_split_last": True, "n_layers": 1},
+                               {"decode": (1, 1, 0, 1, 0, 0, 0, 0), "prefill9": (1, 1, 1, 1, 0, 0, 0, 0),
+                                "prefill70": (1, 1, 1, 1, 0, 0, 0, 0)}),
+}
+
+
+@pytest.mark.parametrize("kind", list(SPAN_LAUNCHES))
+def test_forward_launch_structure(kind):
+    """The kernels one inferd_span_forward call launches, counted per class by the span's event
+    profile, for every kind of span boundary at three call shapes: a 9-row prefill of 3 sequences
+    (the GEMV path, not a decode batch), a pure decode call of the same 3 sequences, and a 70-row
+    prefill (the tiled path).  The expected counts (SPAN_LAUNCHES) follow from the layer structure."""
+    from inferd_amd.ops import PROF_CLASSES
+    from inferd_amd.pipeline import buffer_elems
+    kw, expected = SPAN_LAUNCHES[kind]
+    kw = dict(kw)
+    L = kw.pop("n_layers", 3)
+    plain = kind == "plain"
+    d = R.CONFIGS["qwen3-0.6b"]
+    s = span("qwen3-0.6b", 0 if plain else 1, L, plain, plain, kv_pages=16, max_tokens=128, max_positions=1024, **kw)
+    gen = torch.Generator().manual_seed(53)
+    calls = {"prefill9": [(f"a{i}", n) for i, n in enumerate((4, 3, 2))],
+             "decode": [(f"a{i}", 1) for i in range(3)],
+             "prefill70": [(f"b{i}", n) for i, n in enumerate((30, 23, 17))]}
+    got = {}
+    for shape, reqs in calls.items():
+        M = sum(n for _, n in reqs)
+        pure = shape == "decode"
+        if plain:
+            inp = {"ids": torch.randint(0, d.vocab, (M,), generator=gen)}
+        else:
+            n_in = buffer_elems(d, M, s.gateup_split_first, s.o_split_first, pure, s.qkv_split_first)
+            inp = {"x": (torch.randn(n_in, generator=gen) * 0.5).to(torch.bfloat16)}
+        s.profile_start(256)
+        s.forward(reqs, want_next_ids=plain, **inp)
+        prof = s.profile_stop()
+        got[shape] = tuple(prof[c][1] for c in PROF_CLASSES)
+        print(f"{kind} {shape}: {got[shape]}")
+    s.check_errors()
+    assert got == expected
+
+
 def test_half_layer_span_rejects_bad_configs():
     """A span with the embedding cannot start at a MLP half, one with lm_head cannot end at an
     attention half, a one-layer span cannot skip both halves, and a layer's absent half has no
