@@ -283,8 +283,8 @@ typedef struct InferdSampling {
   uint64_t seed;
   const uint64_t* row_seeds; /* device [n_seqs of the call], NULL: the row index */
 } InferdSampling;
-/* has_lm_head spans only (the vocab-parallel head would need a cross-shard top-k merge); NULL
- * restores greedy.  Afterwards next_ids of inferd_span_forward / _step / _graph_capture is a draw
+/* has_lm_head spans only (the vocab-parallel head samples through inferd_span_head_shard_sampled
+ * below, which takes its parameters per call); NULL restores greedy.  Afterwards next_ids of inferd_span_forward / _step / _graph_capture is a draw
  * with pos = ctx_lens[b] of the call's batch, read on the device (the parameters, row_seeds
  * pointer included, are baked into a graph at capture).  A call that passes no `logits` stores
  * them in a [64][vocab] bf16 buffer of the span, allocated by the first call here.  A span on
@@ -296,6 +296,49 @@ int inferd_span_set_sampling(InferdSpan* span, const InferdSampling* p);
  * overflow). */
 int inferd_sample(const void* logits, int32_t rows, int32_t vocab, const InferdSampling* p,
                   const int32_t* positions, int32_t* ids, float* u_out, int32_t* flags, void* stream);
+
+/* ---- Sampled decoding with the vocab-parallel head (added within ABI 5).  The draw above over a
+ * row whose columns are spread over lm_head shards, with the whole head's result bit for bit: the
+ * same ids, u and overflow flag for every partition of the vocabulary and every shard order (a
+ * logit does not depend on the shard that computes it; DESIGN.md §9 has the merge argument).
+ * The shards chain a CANDIDATE RECORD per row, as the greedy head chains its running max keys.
+ * Over the columns X seen so far, with v_k(X) the min(top_k, |X|)-th largest s in X, the record
+ * holds the first INFERD_SAMPLE_CAND_ENTRIES entries of {c in X : s[c] >= v_k(X)} in the order (s
+ * descending, column ascending).  Layout: device uint64 [rows][1 + INFERD_SAMPLE_CAND_ENTRIES],
+ * 8-byte aligned; word 0 of a row = the entry count n (0 .. 257), words 1 .. n = the entries in
+ * the order, each (order(fp32 s) << 32) | (0xFFFFFFFF - c) with c the GLOBAL column and order()
+ * the monotone 32-bit key of a float (-0 as +0), the remaining words 0.  One entry more than
+ * INFERD_SAMPLE_MAX_KEPT is carried so that "more than INFERD_SAMPLE_MAX_KEPT columns qualify"
+ * (flag bit 2) survives the chain.  A record belongs to one (temperature, top_k): every call of a
+ * chain passes the same InferdSampling; the shards' column ranges must be disjoint.
+ *   cand_in    the record of the shards before this one (NULL: none)
+ *   cand_out   optional: the record including this shard (may alias cand_in)
+ *   ids        optional int32 [rows]: finishes the draw from the record including this shard --
+ *              top-p, renormalisation and the uniform of (seed, row_seed, positions[r]) as above;
+ *              needs positions (device int32 [rows]: the position the drawn token will occupy)
+ *   u_out      optional float [rows], with ids: the uniform used
+ * cand_out or ids is required.  Parameter ranges are checked as above before any device call. */
+#define INFERD_SAMPLE_CAND_ENTRIES 257
+/* bytes of the record of `rows` rows (1 .. 64); -1 otherwise */
+int64_t inferd_sample_cand_bytes(int32_t rows);
+/* one shard of a vocab-parallel SAMPLED head: the span's lm_head shard over `rows` (<= 64) normed
+ * rows (as inferd_span_head_shard), folded into the running candidate record.  `logits` optional:
+ * bf16 [rows][head_rows] row-major, 16-byte aligned (else they go to a buffer of the span).  A span
+ * that owns no lm_head rows runs the record alone (normed may be NULL): the finishing call of a
+ * stage behind the last shard.  Overflow sets the span's sticky flag bit 2.  Stateless: the
+ * parameters are taken per call (and baked into a graph at capture, row_seeds pointer included);
+ * on a has_lm_head span that never sampled the first call without `logits` allocates the buffer,
+ * so make that call before capturing one. */
+int inferd_span_head_shard_sampled(InferdSpan* span, const void* normed, int32_t rows, const InferdSampling* p,
+                                   const void* cand_in, void* cand_out, const int32_t* positions,
+                                   int32_t* ids, float* u_out, void* logits, void* stream);
+/* single op (parity tests, non-span hosts): the same over bf16 logits [rows][cols] row-major holding
+ * the global columns [first_col, first_col + cols); cols % 16 == 0, first_col % 16 == 0, 16-byte
+ * aligned, rows <= 64, cols <= 393216.  cols == 0 (logits may be NULL) runs the record alone: with
+ * ids that finishes a chain from cand_in.  flags optional int32 [1] (bit 2 OR-ed in on overflow). */
+int inferd_sample_shard(const void* logits, int32_t rows, int32_t cols, int32_t first_col, const InferdSampling* p,
+                        const void* cand_in, void* cand_out, const int32_t* positions, int32_t* ids,
+                        float* u_out, int32_t* flags, void* stream);
 
 /* Per-kernel-class timing: HIP events recorded on the launch stream around every kernel of
  * the forward (classes below), up to max_pairs pairs; stop() synchronises on the events

@@ -46,6 +46,7 @@ class Sampling(C.Structure):
 
 
 SAMPLE_MAX_K, SAMPLE_MAX_KEPT = 64, 256   # INFERD_SAMPLE_MAX_K / INFERD_SAMPLE_MAX_KEPT
+SAMPLE_CAND_ENTRIES = 257                 # INFERD_SAMPLE_CAND_ENTRIES (a record row: 1 + that many uint64)
 
 SIGNATURES = {
     "inferd_last_error": (C.c_char_p, []),
@@ -70,6 +71,11 @@ SIGNATURES = {
     "inferd_span_error_flags": (C.c_int, [c_p, C.POINTER(c_i32)]),
     "inferd_span_set_sampling": (C.c_int, [c_p, C.POINTER(Sampling)]),
     "inferd_sample": (C.c_int, [c_p, c_i32, c_i32, C.POINTER(Sampling), c_p, c_p, c_p, c_p, c_p]),
+    "inferd_sample_cand_bytes": (c_i64, [c_i32]),
+    "inferd_span_head_shard_sampled": (C.c_int, [c_p, c_p, c_i32, C.POINTER(Sampling), c_p, c_p, c_p, c_p, c_p, c_p,
+                                                 c_p]),
+    "inferd_sample_shard": (C.c_int, [c_p, c_i32, c_i32, c_i32, C.POINTER(Sampling), c_p, c_p, c_p, c_p, c_p, c_p,
+                                      c_p]),
     "inferd_span_kv_layer": (C.c_int, [c_p, c_i32, C.POINTER(c_p)]),
     "inferd_span_kv_clear": (C.c_int, [c_p, c_p]),
     "inferd_weightgen": (C.c_int, [c_p, c_i64, c_u64, c_u32, c_f, c_f, c_p]),

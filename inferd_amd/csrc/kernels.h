@@ -151,6 +151,18 @@ void launch_argmax_combine(const unsigned long long* keys, int n_parts, int rows
 void launch_sample(const u16* logits, int rows, int vocab, const unsigned long long* keys, float temperature,
                    int top_k, float top_p, uint64_t seed, const uint64_t* row_seeds, const int32_t* positions,
                    int32_t* ids, float* u_out, int32_t* flags, hipStream_t s);
+// One shard of a vocab-parallel sampled head: logits [rows][cols] hold the global columns [first_col,
+// first_col + cols) (cols % 16 == 0, may be 0 with logits null: the record alone), keys their tile
+// keys or null.  The shard's top-k candidates are merged with the running candidate record cand_in
+// (null: none; [rows][SAMPLE_CAND_WORDS] uint64: count, then the first SAMPLE_CAND_ENTRIES entries of
+// {s >= v_k} over the columns seen so far, in the order, zero-filled) into cand_out (may alias
+// cand_in) and / or drawn from (ids, with positions) exactly as launch_sample draws from the whole row.
+#define SAMPLE_CAND_ENTRIES 257
+#define SAMPLE_CAND_WORDS (SAMPLE_CAND_ENTRIES + 1)
+void launch_sample_shard(const u16* logits, int rows, int cols, int first_col, const unsigned long long* keys,
+                         float temperature, int top_k, float top_p, uint64_t seed, const uint64_t* row_seeds,
+                         const int32_t* positions, const unsigned long long* cand_in, unsigned long long* cand_out,
+                         int32_t* ids, float* u_out, int32_t* flags, hipStream_t s);
 
 // attention.hip
 struct AttnBatch {

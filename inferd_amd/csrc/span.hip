@@ -111,7 +111,8 @@ struct InferdSpan {
   unsigned long long* argmax_partial = nullptr;
   // sampled decoding (inferd_span_set_sampling): with sampling_on the head's next_ids are a draw
   // (sampling.hip) instead of argmax_reduce; sample_logits [64][vocab] holds the logits of calls
-  // that pass none (allocated by the first set_sampling)
+  // that pass none (allocated by the first set_sampling; a vocab-parallel shard's [64][head_rows]
+  // for inferd_span_head_shard_sampled at creation: a call there may sit in a graph capture)
   bool sampling_on = false;
   InferdSampling sampling{};
   u16* sample_logits = nullptr;
@@ -306,6 +307,7 @@ extern "C" int inferd_span_create(const InferdSpanConfig* cfg, InferdSpan** out)
   if (hipMemset(s->attn_ws, 0, s->attn_ws_bytes) != hipSuccess) return bail(fail(INFERD_ERR_HIP, "memset failed"));
   SALLOC(s->ssq, (size_t)(2 * c.n_layers) * SSQ_SLOT_WORDS * 8);
   if (s->lm_rows() > 0) SALLOC(s->argmax_partial, (size_t)(s->lm_rows() / 16) * 64 * 8);
+  if (c.head_rows > 0) SALLOC(s->sample_logits, (size_t)64 * c.head_rows * 2);
   SALLOC(s->qkv_part, (size_t)QKV_KSL * 16 * s->qkv_rows() * 4);
   // the prefill tail split's workspace, once (a forward never allocates): only spans whose
   // calls can reach the 256x256 GEMMs (>= 512 rows) need it
@@ -877,6 +879,20 @@ static int check_sampling(const InferdSampling* p) {
   return INFERD_OK;
 }
 
+// the span's [64][lm_rows] logits buffer of sampled calls that pass no `logits`, on the span's own
+// device (where its buffers live), whichever device the caller has current
+static int ensure_sample_logits(InferdSpan* s) {
+  if (s->sample_logits) return INFERD_OK;
+  hipPointerAttribute_t at;
+  int cur = 0;
+  HIP_TRY(hipPointerGetAttributes(&at, s->err));
+  HIP_TRY(hipGetDevice(&cur));
+  if (at.device != cur) HIP_TRY(hipSetDevice(at.device));
+  const int rc = s->alloc((void**)&s->sample_logits, (size_t)64 * s->lm_rows() * 2);
+  if (at.device != cur) (void)hipSetDevice(cur);
+  return rc;
+}
+
 extern "C" int inferd_span_set_sampling(InferdSpan* s, const InferdSampling* p) {
   if (p) {
     const int rc = check_sampling(p);
@@ -888,21 +904,11 @@ extern "C" int inferd_span_set_sampling(InferdSpan* s, const InferdSampling* p) 
     return INFERD_OK;
   }
   if (!s->cfg.has_lm_head)
-    return fail(INFERD_ERR_ARG, "sampling needs a span with the whole lm_head (has_lm_head; the vocab-parallel head "
-                                "is greedy only)");
+    return fail(INFERD_ERR_ARG, "sampling needs a span with the whole lm_head (has_lm_head; a vocab-parallel shard "
+                                "samples per call: inferd_span_head_shard_sampled)");
   if (s->cfg.vocab > SAMPLE_MAX_VOCAB)
     return fail(INFERD_ERR_ARG, "sampling: vocab must be <= " + std::to_string(SAMPLE_MAX_VOCAB));
-  if (!s->sample_logits) {
-    // on the span's own device (where its buffers live), whichever device the caller has current
-    hipPointerAttribute_t at;
-    int cur = 0;
-    HIP_TRY(hipPointerGetAttributes(&at, s->err));
-    HIP_TRY(hipGetDevice(&cur));
-    if (at.device != cur) HIP_TRY(hipSetDevice(at.device));
-    const int rc = s->alloc((void**)&s->sample_logits, (size_t)64 * s->cfg.vocab * 2);
-    if (at.device != cur) (void)hipSetDevice(cur);
-    if (rc) return rc;
-  }
+  if (const int rc = ensure_sample_logits(s)) return rc;
   s->sampling = *p;
   s->sampling_on = true;
   return INFERD_OK;
@@ -919,6 +925,81 @@ extern "C" int inferd_sample(const void* logits, int32_t rows, int32_t vocab, co
   if ((uintptr_t)logits % 16) return fail(INFERD_ERR_ARG, "sample: logits must be 16-byte aligned");
   launch_sample((const u16*)logits, rows, vocab, nullptr, p->temperature, p->top_k, p->top_p, p->seed, p->row_seeds,
                 positions, ids, u_out, flags, (hipStream_t)stream);
+  LAUNCH_CHECK();
+  return INFERD_OK;
+}
+
+// ---- vocab-parallel sampled head: the candidate record chained over the shards (sampling.hip)
+extern "C" int64_t inferd_sample_cand_bytes(int32_t rows) {
+  if (rows < 1 || rows > 64) {
+    g_err = "inferd_sample_cand_bytes: rows 1 .. 64";
+    return -1;
+  }
+  return (int64_t)rows * SAMPLE_CAND_WORDS * 8;
+}
+
+// what both sampled shard calls require of their record / output pointers
+static int check_shard_io(const char* who, const void* cand_in, const void* cand_out, const int32_t* positions,
+                          const int32_t* ids) {
+  if (!cand_out && !ids) return fail(INFERD_ERR_ARG, std::string(who) + ": cand_out or ids is required");
+  if (ids && !positions) return fail(INFERD_ERR_ARG, std::string(who) + ": ids needs positions");
+  if ((uintptr_t)cand_in % 8 || (uintptr_t)cand_out % 8)
+    return fail(INFERD_ERR_ARG, std::string(who) + ": candidate records must be 8-byte aligned");
+  return INFERD_OK;
+}
+
+extern "C" int inferd_sample_shard(const void* logits, int32_t rows, int32_t cols, int32_t first_col,
+                                   const InferdSampling* p, const void* cand_in, void* cand_out,
+                                   const int32_t* positions, int32_t* ids, float* u_out, int32_t* flags, void* stream) {
+  if (!p) return fail(INFERD_ERR_ARG, "sample_shard: null parameters");
+  if (const int rc = check_sampling(p)) return rc;
+  if (rows < 1 || rows > 64) return fail(INFERD_ERR_ARG, "sample_shard: rows 1 .. 64");
+  if (cols < 0 || cols % 16 || cols > SAMPLE_MAX_VOCAB)
+    return fail(INFERD_ERR_ARG, "sample_shard: cols a multiple of 16 up to " + std::to_string(SAMPLE_MAX_VOCAB) +
+                                    " (0: the record alone)");
+  if (first_col < 0 || first_col % 16 || (int64_t)first_col + cols > INT32_MAX)
+    return fail(INFERD_ERR_ARG, "sample_shard: first_col a multiple of 16, >= 0");
+  if (cols > 0 && !logits) return fail(INFERD_ERR_ARG, "sample_shard: logits are required with cols > 0");
+  if (cols > 0 && (uintptr_t)logits % 16) return fail(INFERD_ERR_ARG, "sample_shard: logits must be 16-byte aligned");
+  if (const int rc = check_shard_io("sample_shard", cand_in, cand_out, positions, ids)) return rc;
+  launch_sample_shard(cols ? (const u16*)logits : nullptr, rows, cols, first_col, nullptr, p->temperature, p->top_k,
+                      p->top_p, p->seed, p->row_seeds, positions, (const unsigned long long*)cand_in,
+                      (unsigned long long*)cand_out, ids, u_out, flags, (hipStream_t)stream);
+  LAUNCH_CHECK();
+  return INFERD_OK;
+}
+
+// The span's lm_head shard folded into the running candidate record: the same GEMV and tiles as
+// inferd_span_head_shard (each logit is the one a single lm_head computes), its EPI_ARGMAX tile
+// keys selecting the tiles the shard kernel reads back.  A span owning no rows runs the record
+// alone (a finishing call on the stage behind the last shard).
+extern "C" int inferd_span_head_shard_sampled(InferdSpan* s, const void* normed, int32_t rows, const InferdSampling* p,
+                                              const void* cand_in, void* cand_out, const int32_t* positions,
+                                              int32_t* ids, float* u_out, void* logits, void* stream) {
+  if (!p) return fail(INFERD_ERR_ARG, "head_shard_sampled: null parameters");
+  if (const int rc = check_sampling(p)) return rc;
+  if (!s || rows <= 0 || rows > 64) return fail(INFERD_ERR_ARG, "bad head_shard_sampled args (rows 1..64)");
+  if (const int rc = check_shard_io("head_shard_sampled", cand_in, cand_out, positions, ids)) return rc;
+  const InferdSpanConfig& c = s->cfg;
+  const int n = s->lm_rows();
+  if (n > 0 && !normed) return fail(INFERD_ERR_ARG, "head_shard_sampled: normed rows are required");
+  if (n > SAMPLE_MAX_VOCAB) return fail(INFERD_ERR_ARG, "sampling: vocab must be <= " + std::to_string(SAMPLE_MAX_VOCAB));
+  if (logits && (n == 0 || (uintptr_t)logits % 16))
+    return fail(INFERD_ERR_ARG, "head_shard_sampled: `logits` needs a span with lm_head rows and 16-byte alignment");
+  hipStream_t st = (hipStream_t)stream;
+  u16* lg = (u16*)logits;
+  if (n > 0 && !lg) {
+    if (const int rc = ensure_sample_logits(s)) return rc;  // has_lm_head spans only: shards own one from creation
+    lg = s->sample_logits;
+  }
+  const long pe = s->prof_begin(PROF_LMHEAD, st);
+  if (n > 0)
+    GEMM_TRY(launch_gemm((const u16*)normed, c.hidden, s->lm_head, rows, n, c.hidden, lg, n, nullptr, 0, EPI_ARGMAX,
+                         s->argmax_partial, st, nullptr, nullptr, nullptr, GEMM_PACK_A));
+  launch_sample_shard(lg, rows, n, s->lm_first(), n > 0 ? s->argmax_partial : nullptr, p->temperature, p->top_k,
+                      p->top_p, p->seed, p->row_seeds, positions, (const unsigned long long*)cand_in,
+                      (unsigned long long*)cand_out, ids, u_out, s->err, st);
+  s->prof_end(pe, st);
   LAUNCH_CHECK();
   return INFERD_OK;
 }

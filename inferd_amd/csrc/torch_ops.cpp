@@ -274,6 +274,85 @@ void span_head_shard(int64_t span, const at::Tensor& normed, int64_t rows, const
      "span_head_shard");
 }
 
+// ---- vocab-parallel sampled head (inferd_sample_cand_bytes / _span_head_shard_sampled / _sample_shard).
+// Candidate records are int64 tensors holding the uint64 words, [rows, 1 + INFERD_SAMPLE_CAND_ENTRIES].
+int64_t sample_cand_bytes(int64_t rows) {
+  const int64_t b = inferd_sample_cand_bytes((int32_t)std::min<int64_t>(std::max<int64_t>(rows, 0), 65));
+  TORCH_CHECK(b > 0, "sample_cand_bytes: ", inferd_last_error());
+  return b;
+}
+
+// the record / output buffers both sampled shard ops share, against `rows`
+void check_shard_args(at::Device dev, int64_t rows, const std::optional<at::Tensor>& row_seeds,
+                      const std::optional<at::Tensor>& cand_in, const std::optional<at::Tensor>& cand_out,
+                      const std::optional<at::Tensor>& positions, const std::optional<at::Tensor>& ids,
+                      const std::optional<at::Tensor>& u_out) {
+  const int64_t words = rows * (1 + INFERD_SAMPLE_CAND_ENTRIES);
+  check_arg(row_seeds, dev, at::kLong, rows, "row_seeds");
+  check_arg(cand_in, dev, at::kLong, words, "cand_in");
+  check_arg(cand_out, dev, at::kLong, words, "cand_out");
+  check_arg(positions, dev, at::kInt, rows, "positions");
+  check_arg(ids, dev, at::kInt, rows, "ids");
+  check_arg(u_out, dev, at::kFloat, rows, "u_out");
+  TORCH_CHECK(!u_out || ids, "u_out needs ids");
+}
+
+// the span's shard of a sampled vocab-parallel head over `rows` final-normed rows (as span_head_shard),
+// folded into the running candidate record; ids (with positions) finishes the draw
+void span_head_shard_sampled(int64_t span, const at::Tensor& normed, int64_t rows, double temperature, int64_t top_k,
+                             double top_p, int64_t seed, const std::optional<at::Tensor>& row_seeds,
+                             const std::optional<at::Tensor>& cand_in, const std::optional<at::Tensor>& cand_out,
+                             const std::optional<at::Tensor>& positions, const std::optional<at::Tensor>& ids,
+                             const std::optional<at::Tensor>& u_out, const std::optional<at::Tensor>& logits) {
+  InferdSpan* s = handle<InferdSpan>(span, "span_head_shard_sampled");
+  const InferdSpanConfig c = config_of(s);
+  const int64_t n = c.has_lm_head ? c.vocab : c.head_rows;
+  TORCH_CHECK(rows >= 1 && rows <= 64, "span_head_shard_sampled: 1 .. 64 rows");
+  TORCH_CHECK(top_k >= INT32_MIN && top_k <= INT32_MAX, "span_head_shard_sampled: top_k out of range");
+  TORCH_CHECK(normed.is_cuda(), "span_head_shard_sampled: normed must be on a GPU");
+  const at::Device dev = normed.device();
+  check_arg(normed, dev, at::kBFloat16, (rows + 15) / 16 * 16 * (int64_t)c.hidden, "normed");
+  check_shard_args(dev, rows, row_seeds, cand_in, cand_out, positions, ids, u_out);
+  TORCH_CHECK(!logits || n > 0, "span_head_shard_sampled: logits need a span with lm_head rows");
+  check_arg(logits, dev, at::kBFloat16, rows * n, "logits");
+  const InferdSampling p{(float)temperature, (int32_t)top_k, (float)top_p, (uint64_t)seed,
+                         (const uint64_t*)opt_ptr(row_seeds)};
+  c10::hip::HIPGuard g(dev.index());
+  ok(inferd_span_head_shard_sampled(s, normed.data_ptr(), (int32_t)rows, &p, opt_ptr(cand_in), (void*)opt_ptr(cand_out),
+                                    (const int32_t*)opt_ptr(positions), (int32_t*)opt_ptr(ids), (float*)opt_ptr(u_out),
+                                    (void*)opt_ptr(logits), stream_of(dev)),
+     "span_head_shard_sampled");
+}
+
+// the single op (inferd_sample_shard): logits bf16 [rows, cols] = the global columns [first_col,
+// first_col + cols), or None (cols = 0: the record cand_in alone)
+void sample_shard(const std::optional<at::Tensor>& logits, int64_t rows, int64_t first_col, double temperature,
+                  int64_t top_k, double top_p, int64_t seed, const std::optional<at::Tensor>& row_seeds,
+                  const std::optional<at::Tensor>& cand_in, const std::optional<at::Tensor>& cand_out,
+                  const std::optional<at::Tensor>& positions, const std::optional<at::Tensor>& ids,
+                  const std::optional<at::Tensor>& u_out, const std::optional<at::Tensor>& flags) {
+  TORCH_CHECK(logits || cand_in, "sample_shard: logits or cand_in is required");
+  const at::Tensor& any = logits ? *logits : *cand_in;
+  TORCH_CHECK(any.is_cuda(), "sample_shard: GPU tensors");
+  TORCH_CHECK(!logits || (logits->dim() == 2 && logits->size(0) == rows), "sample_shard: logits must be [rows, cols]");
+  TORCH_CHECK(rows >= 1 && rows <= 64, "sample_shard: 1 .. 64 rows");
+  TORCH_CHECK(top_k >= INT32_MIN && top_k <= INT32_MAX && first_col >= INT32_MIN && first_col <= INT32_MAX,
+              "sample_shard: top_k / first_col out of range");
+  const at::Device dev = any.device();
+  const int64_t cols = logits ? logits->size(1) : 0;
+  TORCH_CHECK(cols <= INT32_MAX, "sample_shard: cols out of range");
+  check_arg(logits, dev, at::kBFloat16, 0, "logits");
+  check_shard_args(dev, rows, row_seeds, cand_in, cand_out, positions, ids, u_out);
+  check_arg(flags, dev, at::kInt, 1, "flags");
+  const InferdSampling p{(float)temperature, (int32_t)top_k, (float)top_p, (uint64_t)seed,
+                         (const uint64_t*)opt_ptr(row_seeds)};
+  c10::hip::HIPGuard g(dev.index());
+  ok(inferd_sample_shard(opt_ptr(logits), (int32_t)rows, (int32_t)cols, (int32_t)first_col, &p, opt_ptr(cand_in),
+                         (void*)opt_ptr(cand_out), (const int32_t*)opt_ptr(positions), (int32_t*)opt_ptr(ids),
+                         (float*)opt_ptr(u_out), (int32_t*)opt_ptr(flags), stream_of(dev)),
+     "sample_shard");
+}
+
 // greedy ids from n_parts shards' keys int64 [n_parts, rows] -> ids int32 [rows]
 void argmax_combine(const at::Tensor& keys, int64_t n_parts, int64_t rows, const at::Tensor& ids) {
   TORCH_CHECK(keys.is_cuda() && n_parts >= 1 && rows >= 1, "argmax_combine: GPU keys, n_parts >= 1, rows >= 1");
@@ -477,6 +556,12 @@ struct DecodeGraph : torch::CustomClassHolder {
        "DecodeGraph.launch_eager: kv_advance");
   }
   int64_t steps_left() const { return n_steps - launched; }
+  // the descriptor's ctx_lens [sequences] (a view of the device words the graph's scheduler step
+  // advances): after a step, the position the token drawn from it will occupy
+  at::Tensor ctx_lens() const {
+    const int64_t n = (int64_t)seqs.size();
+    return words.narrow(0, 3 * n + 1, n);
+  }
 };
 
 }  // namespace
@@ -504,6 +589,15 @@ TORCH_LIBRARY(inferd, m) {
         "Tensor(b!)? ids, Tensor(c!)? logits=None) -> ()",
         &span_head_shard);
   m.def("argmax_combine(Tensor keys, int n_parts, int rows, Tensor(a!) ids) -> ()", &argmax_combine);
+  m.def("sample_cand_bytes(int rows) -> int", &sample_cand_bytes);
+  m.def("span_head_shard_sampled(int span, Tensor normed, int rows, float temperature, int top_k, float top_p, "
+        "int seed, Tensor? row_seeds, Tensor? cand_in, Tensor(a!)? cand_out, Tensor? positions, Tensor(b!)? ids, "
+        "Tensor(c!)? u_out=None, Tensor(d!)? logits=None) -> ()",
+        &span_head_shard_sampled);
+  m.def("sample_shard(Tensor? logits, int rows, int first_col, float temperature, int top_k, float top_p, int seed, "
+        "Tensor? row_seeds, Tensor? cand_in, Tensor(a!)? cand_out, Tensor? positions, Tensor(b!)? ids, "
+        "Tensor(c!)? u_out=None, Tensor(d!)? flags=None) -> ()",
+        &sample_shard);
   m.def("dedicated_stream(Device device) -> int", &dedicated_stream);
   m.def("weightgen(Tensor(a!) dst, int seed, int tensor_id, float scale, float center) -> ()", &weightgen);
   m.def("kv_create(int n_pages) -> int", &kv_create);
@@ -521,5 +615,6 @@ TORCH_LIBRARY(inferd, m) {
                        std::optional<at::Tensor>, at::Device>())
       .def("launch", &DecodeGraph::launch)
       .def("launch_eager", &DecodeGraph::launch_eager)
-      .def("steps_left", &DecodeGraph::steps_left);
+      .def("steps_left", &DecodeGraph::steps_left)
+      .def("ctx_lens", &DecodeGraph::ctx_lens);
 }

@@ -31,7 +31,8 @@ ops = torch.ops.inferd
 
 OPS = ("span_create", "span_destroy", "span_config", "span_init_synthetic", "span_set_weight", "span_error_flags",
        "span_profile_start", "span_profile_stop", "span_forward", "span_lm_head", "span_head_shard", "argmax_combine",
-       "span_set_sampling", "sample", "dedicated_stream",
+       "span_set_sampling", "sample", "sample_cand_bytes", "span_head_shard_sampled", "sample_shard",
+       "dedicated_stream",
        "weightgen", "kv_create",
        "kv_destroy", "kv_reserve", "kv_advance", "kv_release", "kv_query", "kv_pages", "kv_free_pages",
        "kv_build_batch")

@@ -300,7 +300,8 @@ class PartitionedQwen2:
     call (SpanRuntime.set_sampling) and clears it afterwards, so next_token_id is a draw at the
     token's position with the row seed session_row_seed(session_id) (0 for a stateless call): the
     same seed, session and prefix give the same token on any node.  Without the key the answer
-    is greedy.  A stage whose head is vocab-parallel raises ValueError (that head is greedy only)."""
+    is greedy.  A stage whose head is vocab-parallel raises ValueError (that head samples through
+    SpanRuntime.head_shard_sampled / PipelineStage(sampling=...), not through this chain)."""
 
     def __init__(self, model_name: str, num_stages: int, stage: int, parts_path: str):
         self.stage = stage
@@ -369,8 +370,8 @@ class PartitionedQwen2:
     def _sampling(self, inputs):
         sampling = _sampling_of(inputs)
         if sampling is not None and (self.span.head_rows or self.span.final_norm_out):
-            raise ValueError('"sampling" needs the last stage to own the whole lm_head: the vocab-parallel head is '
-                             "greedy only")
+            raise ValueError('"sampling" needs the last stage to own the whole lm_head: this chain does not carry the '
+                             "vocab-parallel head's candidate record (SpanRuntime.head_shard_sampled)")
         return sampling
 
     def _sampling_extra(self, sampling):

@@ -31,7 +31,7 @@ import time
 
 import torch
 
-from .runtime import KV_PAGE, DecodeGraph, ModelDims, SpanRuntime
+from .runtime import KV_PAGE, SAMPLE_CAND_WORDS, DecodeGraph, ModelDims, SpanRuntime, check_sampling_params
 
 
 def record_elems(dims, rows: int) -> int:
@@ -585,10 +585,21 @@ class SpanExecutor:
         self.dims = span.dims
         self.has_embed, self.has_lm_head = span.has_embed, span.has_lm_head
         self.graphs = []
+        self.sampling = self.row_seeds = None
 
-    def prefill(self, sessions, n_tokens, ids=None, x=None, want_ids=False, want_logits=False):
+    def set_sampling(self, sampling, row_seeds):
+        """Sampled decoding (PipelineStage(sampling=...)): (temperature, top_k, top_p, seed) and, per
+        microbatch, the int64 device tensor of its rows' seeds.  With the whole head the span draws its
+        next_ids (SpanRuntime.set_sampling, pointed at the item's row seeds before each call); with a
+        vocab-parallel head head_sampled() is this stage's shard."""
+        self.sampling, self.row_seeds = tuple(sampling), row_seeds
+
+    def prefill(self, sessions, n_tokens, ids=None, x=None, want_ids=False, want_logits=False, row_seeds=None):
         """`sessions` each get n_tokens new tokens (ids on the first span, x otherwise).  Returns
-        the hidden rows, or (last span) the greedy ids -- with want_logits (ids, last-row logits)."""
+        the hidden rows, or (last span) the greedy ids -- with want_logits (ids, last-row logits).
+        row_seeds (a sampled whole head): the sessions' row seeds; the ids are draws."""
+        if want_ids and self.sampling is not None:
+            self.span.set_sampling(*self.sampling, row_seeds=row_seeds)
         out = self.span.forward([(sid, n_tokens) for sid in sessions], ids=ids, x=x,
                                 want_hidden=not want_ids, want_next_ids=want_ids, want_logits=want_logits)
         if want_ids:
@@ -598,10 +609,19 @@ class SpanExecutor:
     def prepare_decode(self, microbatches, n_steps, bufs):
         """Capture one decode graph per microbatch over its fixed buffers
         (bufs[m]: dict with ids / x / hidden_out / next_ids device tensors or None)."""
-        self.graphs = [DecodeGraph(self.span, sessions, n_steps, **bufs[m])
-                       for m, sessions in enumerate(microbatches)]
+        self.graphs = []
+        for m, sessions in enumerate(microbatches):
+            if self._draws:      # the microbatch's row seeds are baked into its graph
+                self.span.set_sampling(*self.sampling, row_seeds=self.row_seeds[m])
+            self.graphs.append(DecodeGraph(self.span, sessions, n_steps, **bufs[m]))
+
+    @property
+    def _draws(self) -> bool:
+        return self.sampling is not None and self.has_lm_head
 
     def decode(self, m):
+        if self._draws and self.eager:     # an eager step reads the span's current setting
+            self.span._point_seeds(self.row_seeds[m])
         if self.eager:
             self.graphs[m].launch_eager()
         else:
@@ -610,6 +630,15 @@ class SpanExecutor:
     def head(self, normed, rows, keys_in=None, keys_out=None, ids=None):
         """This span's lm_head shard over `rows` normed rows (vocab-parallel head; SpanRuntime.head_shard)."""
         self.span.head_shard(normed, rows, keys_in, keys_out, ids)
+
+    def head_sampled(self, normed, rows, m, cand_in=None, cand_out=None, ids=None, positions=None):
+        """This span's shard of microbatch m's SAMPLED vocab-parallel head (SpanRuntime.head_shard_sampled):
+        its candidates folded into the running record; `ids` finishes the draw at `positions` (default:
+        the microbatch's device ctx_lens -- after its decode step, the position the drawn token takes)."""
+        if ids is not None and positions is None:
+            positions = self.graphs[m].ctx_lens
+        self.span.head_shard_sampled(normed, rows, self.sampling, self.row_seeds[m], cand_in=cand_in,
+                                     cand_out=cand_out, positions=positions, ids=ids)
 
     @staticmethod
     def combine(keys, n_parts, rows, ids):
@@ -749,7 +778,15 @@ class PipelineStage:
     running keys it forwards; the last stage's shard finishes the argmax and sends the ids to stage
     0.  Every hand-off stays on the ring's own edges (one inbound and one outbound communicator per
     GPU).  Item j's ids reach stage 0 S iterations after its normed rows left the last stage, 2S
-    iterations after stage 0 ran its layers: n_mb = 2S + slack."""
+    iterations after stage 0 ran its layers: n_mb = 2S + slack.
+
+    Sampled (sampling=(temperature, top_k, top_p, seed)): every next token is a draw instead of the
+    argmax.  With the whole head the last stage's span draws (SpanRuntime.set_sampling); with the
+    vocab-parallel head the running keys of the head record are replaced by the candidate record of
+    include/inferd_span.h (33 KB instead of 128 B at B = 16), every stage's shard folds its top-k
+    candidates in (SpanRuntime.head_shard_sampled) and the last stage's call finishes the draw at the
+    positions in the microbatch's device ctx_lens.  Same messages, same order; the ids are the whole
+    head's bit for bit."""
 
     def __init__(self, dims: ModelDims, rank: int, world: int, first_layer: int, n_layers: int, *,
                  device, seed: int, n_microbatches: int, batch: int, max_ctx: int, prefill_chunk: int = 2,
@@ -757,7 +794,7 @@ class PipelineStage:
                  skip_first_attn: bool = False, skip_last_mlp: bool = False, gateup_split_first: int = 0,
                  gateup_split_last: int = 0, o_split_first: bool = False, o_split_last: bool = False,
                  qkv_split_first: bool = False, qkv_split_last: bool = False, eager_decode: bool = True,
-                 sharded_head: bool = False, head_shard=(0, 0)):
+                 sharded_head: bool = False, head_shard=(0, 0), sampling=None):
         """profile: the synthetic weight profile (runtime.SpanRuntime.init_synthetic: "peaked"
         for token-exact parity runs).  want_logits (last stage, whole head only): every decode step's
         and the prefill's last-row logits are kept, for parity checks against the oracle's.
@@ -766,7 +803,16 @@ class PipelineStage:
         n_microbatches: >= world (ring_microbatches(world, sharded_head) adds the ring's slack).
         sharded_head / head_shard: the greedy head vocab-parallel over the stages, this stage owning
         lm_head rows [head_shard[0], head_shard[0] + head_shard[1]) -- the shards in stage order,
-        contiguous from row 0 (head_shard_split)."""
+        contiguous from row 0 (head_shard_split).
+        sampling: None (greedy: exactly the launches of a pipeline without it) or (temperature, top_k,
+        top_p, seed): every next token is a draw (include/inferd_span.h "Sampled decoding"), row b of
+        microbatch m under row seed m * batch + b, at the position the token will occupy -- with the whole
+        head on the last stage (SpanRuntime.set_sampling) or the vocab-parallel head, whose head record
+        then carries a candidate record instead of the running keys; the ids are the same bit for bit."""
+        if sampling is not None:
+            sampling = (float(sampling[0]), int(sampling[1]), float(sampling[2]), int(sampling[3]))
+            check_sampling_params(*sampling[:3])
+        self.sampling = sampling
         assert n_microbatches >= world * (2 if sharded_head and world > 1 else 1), \
             "the ring needs a microbatch per stage in flight (two with a vocab-parallel head)"
         assert not (sharded_head and want_logits), "logits capture needs the whole head on the last stage"
@@ -794,6 +840,10 @@ class PipelineStage:
             executor = SpanExecutor(span, eager=eager_decode)
         self.ex = executor
         self.span = getattr(executor, "span", None)
+        if sampling is not None:
+            self.row_seeds = [torch.arange(m * batch, (m + 1) * batch, dtype=torch.int64, device=self.device)
+                              for m in range(n_microbatches)]
+            self.ex.set_sampling(sampling, self.row_seeds)
         self.sessions = [[("mb", m, b) for b in range(batch)] for m in range(n_microbatches)]
         h = dims.hidden
         dev = self.device
@@ -811,12 +861,14 @@ class PipelineStage:
         self.h_out = [buf(self.col_out, self.o_out, self.q_out) for _ in mb]
         self.ids_out = [torch.zeros(batch, dtype=torch.int32, device=dev) for _ in mb]
         # vocab-parallel head: the last stage's final-normed rows (fragment-packed 16-row tiles) and
-        # every stage's head record [normed rows | running keys int64 [B]] (bytes)
+        # every stage's head record [normed rows | running keys int64 [B]] (bytes); sampled: [normed
+        # rows | candidate record int64 [B, 258]] (inferd_sample_cand_bytes)
         self.normed_bytes = (batch + 15) // 16 * 16 * h * 2
+        self.key_bytes = 8 * batch * (SAMPLE_CAND_WORDS if sampling is not None else 1)
         if self.sharded:
             self.normed = [torch.zeros(self.normed_bytes // 2, dtype=torch.bfloat16, device=dev) for _ in mb] \
                 if last else None
-            self.head_rec = [torch.zeros(self.normed_bytes + 8 * batch, dtype=torch.uint8, device=dev) for _ in mb]
+            self.head_rec = [torch.zeros(self.normed_bytes + self.key_bytes, dtype=torch.uint8, device=dev) for _ in mb]
         self.want_logits = want_logits and last
         self.logits = [torch.zeros(batch, dims.vocab, dtype=torch.bfloat16, device=dev) for _ in mb] \
             if self.want_logits else None
@@ -858,7 +910,7 @@ class PipelineStage:
         return rec[:self.normed_bytes].view(torch.bfloat16)
 
     def head_keys(self, rec):
-        return rec[self.normed_bytes:self.normed_bytes + 8 * self.B].view(torch.int64)
+        return rec[self.normed_bytes:self.normed_bytes + self.key_bytes].view(torch.int64)
 
     # ------------------------------------------------------------------ ring links
     def _global(self, r: int) -> int:
@@ -1052,13 +1104,19 @@ class PipelineStage:
                   f" {(time.perf_counter() - t0) * 1e3:.1f} ms)", file=sys.stderr, flush=True)
 
     # ------------------------------------------------------------------ head (vocab-parallel)
-    def _head(self, normed, keys_in, keys_out, ids):
+    def _head(self, normed, keys_in, keys_out, ids, m=0, positions=None):
         """This stage's lm_head shard over the B normed rows, folded into the running keys (or the
         ids on the last stage).  Shards run in stage order from row 0 (head_shard_split), so the
         running keys are live iff an earlier stage owns rows (head_first > 0): the first stage with
-        rows starts them, a stage without rows passes the record on untouched."""
+        rows starts them, a stage without rows passes the record on untouched.  Sampled: the keys are
+        microbatch m's candidate record, and ids a draw at `positions` (default: the microbatch's device
+        ctx_lens); a last stage without rows finishes from the record alone."""
         live = self.head_first > 0
-        if self.head_rows:
+        if self.sampling is not None:
+            if self.head_rows or ids is not None:
+                self.ex.head_sampled(normed, self.B, m, cand_in=keys_in if live else None, cand_out=keys_out, ids=ids,
+                                     positions=positions)
+        elif self.head_rows:
             self.ex.head(normed, self.B, keys_in=keys_in if live else None, keys_out=keys_out, ids=ids)
         elif ids is not None:
             self.ex.combine(keys_in, 1, self.B, ids)
@@ -1115,6 +1173,8 @@ class PipelineStage:
                 wl = self.want_logits and capture is not None
                 kw = {"want_logits": True} if wl else {}
                 want_ids = self.last and not self.sharded
+                if want_ids and self.sampling is not None:
+                    kw["row_seeds"] = self.row_seeds[m][c:c + len(sess)]
                 if self.first:
                     ids = prompts[m][c:c + len(sess)].reshape(-1).to(self.device, torch.int32)
                     out = self.ex.prefill(sess, T, ids=ids, want_ids=want_ids, **kw)
@@ -1130,7 +1190,7 @@ class PipelineStage:
                     if capture is not None and i_cur == 0:     # h1 rows (the head of a record)
                         capture["hidden"] = out.reshape(-1)[:len(sess) * T * h].reshape(len(sess) * T, h).cpu()
         if self.sharded:
-            self._prefill_head(ids_parts)
+            self._prefill_head(ids_parts, T)
             return
         if self.last:
             for m in range(self.n_mb):
@@ -1153,13 +1213,16 @@ class PipelineStage:
                 for m in range(self.n_mb):
                     self.ids[m].copy_(flat[m * self.B:(m + 1) * self.B])
 
-    def _prefill_head(self, normed_parts):
+    def _prefill_head(self, normed_parts, T):
         """The vocab-parallel head of every microbatch's prompt (its last rows): the last stage's
         normed rows go to stage 0 and along the ring through every shard, the last stage finishes
         the argmax and returns the first decode ids to stage 0 -- one microbatch at a time on the
         pipeline's group (untimed)."""
         S, h, B = self.S, self.dims.hidden, self.B
         full = {}
+        # a sampled head draws the first decode token: it will occupy position T
+        pos = torch.full((B,), T, dtype=torch.int32, device=self.device) if self.sampling is not None and self.last \
+            else None
         if self.last:     # each chunk's packed rows -> the microbatch's B rows, packed
             for m in range(self.n_mb):
                 rows = [unpack_rows(normed_parts[(m, c)].reshape(-1), min(self.prefill_chunk, B - c), h)
@@ -1172,15 +1235,15 @@ class PipelineStage:
             if self.last:
                 self._exchange(send=full[m], send_to=0)
                 self._exchange(recv=rec, recv_from=S - 2)
-                self._head(full[m], self.head_keys(rec), None, self.ids_out[m])
+                self._head(full[m], self.head_keys(rec), None, self.ids_out[m], m, pos)
                 self._exchange(send=self.ids_out[m], send_to=0)
                 continue
             if self.first:
                 self._exchange(recv=self.head_normed(rec), recv_from=S - 1)
-                self._head(self.head_normed(rec), None, self.head_keys(rec), None)
+                self._head(self.head_normed(rec), None, self.head_keys(rec), None, m)
             else:
                 self._exchange(recv=rec, recv_from=self.rank - 1)
-                self._head(self.head_normed(rec), self.head_keys(rec), self.head_keys(rec), None)
+                self._head(self.head_normed(rec), self.head_keys(rec), self.head_keys(rec), None, m)
             self._exchange(send=rec, send_to=self.rank + 1)
             if self.first:
                 self._exchange(recv=self.ids[m], recv_from=S - 1)
@@ -1268,13 +1331,13 @@ class PipelineStage:
                 rec = self.head_rec[mj]
                 if self.last:
                     self._settle(("ids_out", mj))
-                    self._head(self.normed[mj], self.head_keys(rec), None, self.ids_out[mj])
+                    self._head(self.normed[mj], self.head_keys(rec), None, self.ids_out[mj], mj)
                     self._used(("head", mj))
                     tx = time.perf_counter()
                     self._send(("ids_out", mj), self.ids_out[mj])
                 else:
                     self._head(self.head_normed(rec), None if self.first else self.head_keys(rec),
-                               self.head_keys(rec), None)
+                               self.head_keys(rec), None, mj)
                     self._used(("head", mj))
                     tx = time.perf_counter()
                     self._send(("head", mj), rec)
@@ -1303,9 +1366,12 @@ class PipelineStage:
         if self.sharded:
             rec = self.head_rec[0]
             normed = self.normed[0] if self.last else self.head_normed(rec)
+            # a sampled head's finishing call draws at a fixed position here (timings only)
+            pos = torch.zeros(self.B, dtype=torch.int32, device=self.device) \
+                if self.sampling is not None and self.last else None
             head = lambda: self._head(normed, self.head_keys(rec) if not self.first else None,  # noqa: E731
                                       None if self.last else self.head_keys(rec),
-                                      self.ids_out[0] if self.last else None)
+                                      self.ids_out[0] if self.last else None, 0, pos)
         with self._compute():
             return self.ex.profile_decode(self.sessions, [self._bufs(m) for m in range(self.n_mb)], n_steps, head)
 

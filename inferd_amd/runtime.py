@@ -127,6 +127,44 @@ def sample(logits: torch.Tensor, temperature: float, top_k: int, top_p: float, s
     return (ids, u) if want_u else ids
 
 
+SAMPLE_CAND_WORDS = 1 + 257   # 1 + INFERD_SAMPLE_CAND_ENTRIES: int64 words of one row's candidate record
+
+
+def cand_record(rows: int, device) -> torch.Tensor:
+    """An empty candidate record for `rows` rows of a sampled vocab-parallel head: int64 [rows, 258]
+    (inferd_sample_cand_bytes; count 0)."""
+    assert T.sample_cand_bytes(rows) == rows * SAMPLE_CAND_WORDS * 8
+    return torch.zeros(rows, SAMPLE_CAND_WORDS, dtype=torch.int64, device=device)
+
+
+def sample_shard(logits, first_col: int, temperature: float, top_k: int, top_p: float, seed: int, *, rows=None,
+                 cand_in=None, cand_out=None, positions=None, row_seeds=None, want_ids: bool = False,
+                 want_u: bool = False, flags: torch.Tensor | None = None):
+    """One shard of a sampled vocab-parallel head as a single op (torch.ops.inferd.sample_shard;
+    include/inferd_span.h "Sampled decoding with the vocab-parallel head"): `logits` bf16 [rows <= 64,
+    cols] hold the global columns [first_col, first_col + cols) -- or None with rows given: the
+    record cand_in alone.  Its top-k candidates are merged with the candidate record cand_in (int64
+    [rows, 258], None: no earlier shard) into cand_out (cand_record(); may be cand_in) and, with
+    want_ids (needs positions), the draw is finished from the merged record: chained over disjoint
+    shards covering the vocabulary, in any order, the ids / uniforms / flag are sample()'s on the
+    whole logits bit for bit.  Returns None, ids, or (ids, u) with want_u.  Stream ordered, no sync."""
+    check_sampling_params(temperature, top_k, top_p)
+    if logits is None and cand_in is None:
+        raise ValueError("sample_shard: logits (possibly [rows, 0]) or cand_in is required")
+    dev = logits.device if logits is not None else cand_in.device
+    with torch.cuda.device(dev):
+        lg = None if logits is None else logits.to(torch.bfloat16).contiguous()
+        n = int(rows) if lg is None else lg.shape[0]
+        pos = None if positions is None else \
+            torch.as_tensor(positions).to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+        rs = None if row_seeds is None else row_seed_tensor(row_seeds, dev)
+        ids = torch.empty(n, dtype=torch.int32, device=dev) if want_ids else None
+        u = torch.empty(n, dtype=torch.float32, device=dev) if want_ids and want_u else None
+        T.sample_shard(lg, n, int(first_col), float(temperature), int(top_k), float(top_p), _i64(seed), rs, cand_in,
+                       cand_out, pos, ids, u, flags)
+    return (ids, u) if u is not None else ids
+
+
 class Batch:
     """A batch descriptor: the device (or host) int32 words [seq_start | positions | slots |
     ctx_lens | block_table] the native table wrote and their shape [n_seqs, n_tokens, max_q_len,
@@ -244,6 +282,12 @@ class DecodeGraph:
     @property
     def launched(self) -> int:
         return self.n_steps - self.graph.steps_left()
+
+    @property
+    def ctx_lens(self) -> torch.Tensor:
+        """device int32 [sessions]: the cached lengths the graph's scheduler step advances -- after a
+        step, the position the token drawn from that step will occupy (a view, not a copy)"""
+        return self.graph.ctx_lens()
 
     def launch(self, stream=None):
         if stream is None:
@@ -416,10 +460,11 @@ class SpanRuntime:
         of this list when it cuts the requests into several engine calls; run() and a DecodeGraph
         read them by the row of their batch.  Pass distinct seeds when one batch is split over
         several forward / run calls (pipeline microbatches), or a session's draws would repeat
-        another's.  Spans with the whole lm_head only."""
+        another's.  Spans with the whole lm_head only (a vocab-parallel shard: head_shard_sampled)."""
         check_sampling_params(temperature, top_k, top_p)
         if not self.has_lm_head:
-            raise ValueError("sampling needs the span with the whole lm_head (the vocab-parallel head is greedy only)")
+            raise ValueError("sampling needs the span with the whole lm_head (a vocab-parallel shard samples per call: "
+                             "head_shard_sampled)")
         with torch.cuda.device(self.device):
             rs = None if row_seeds is None else row_seed_tensor(row_seeds, self.device)
             T.span_set_sampling(self.handle, float(temperature), int(top_k), float(top_p), _i64(seed), rs, True)
@@ -496,6 +541,24 @@ class SpanRuntime:
         head rows] -- every output optional (torch.ops.inferd.span_head_shard; stream ordered, no
         sync).  Chained over all shards, the ids are argmax over the whole vocabulary."""
         T.span_head_shard(self.handle, normed, rows, keys_in, keys_out, ids, logits)
+
+    def head_shard_sampled(self, normed: torch.Tensor, rows: int, sampling, row_seeds: torch.Tensor | None = None,
+                           cand_in: torch.Tensor | None = None, cand_out: torch.Tensor | None = None,
+                           positions: torch.Tensor | None = None, ids: torch.Tensor | None = None,
+                           u_out: torch.Tensor | None = None, logits: torch.Tensor | None = None):
+        """head_shard for a SAMPLED vocab-parallel head: this span's lm_head rows over `rows`
+        final-normed rows, their top-k candidates merged with the running candidate record cand_in
+        (int64 [rows, 258], None: no earlier shard) into cand_out (cand_record(); may be cand_in);
+        ids int32 [rows], with positions int32 [rows] (the position each drawn token will occupy),
+        finishes the draw.  sampling = (temperature, top_k, top_p, seed), row_seeds an int64 device
+        tensor [rows] (row_seed_tensor; None: the row index) -- per call, the span keeps no setting.
+        A span owning no lm_head rows passes the record on / finishes from it.  Chained over all
+        shards in any order the ids are a whole-head span's set_sampling draws bit for bit
+        (torch.ops.inferd.span_head_shard_sampled; stream ordered, no sync)."""
+        t, k, p, seed = sampling
+        check_sampling_params(t, k, p)
+        T.span_head_shard_sampled(self.handle, normed, rows, float(t), int(k), float(p), _i64(seed), row_seeds,
+                                  cand_in, cand_out, positions, ids, u_out, logits)
 
     @torch.no_grad()
     def lm_head(self, hidden: torch.Tensor) -> torch.Tensor:
